@@ -10,10 +10,15 @@ A step = one features->depth pass (one call of mvs_depth_from_features_f32) of t
 cost volume -> RegNetUS0 -> soft-argmin + probability map, inputs (feature maps, cameras, weights)
 resident in HBM.  Reference views are independent, so ranks shard them with no
 data-path collective ("scaling": "weak"); value = depth maps of all ranks / max-over-ranks time.
-Rank 0 prints ONE JSON line.  After the timed region (never inside it) the same process adds informative records
-to that line: the median of repeated blocks of the same K steps, in-pipeline times of every RegNetUS0 layer
-(`roofline_kernels`), and -- single GPU only -- configs[1] (c2, 288x216, D=192) and configs[2] (c3, ConvGRU sweep,
-400x300, D=256) with their rates and their distance from the committed float64 fixtures (tests/golden/full_*.npz).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints that line (the headline
+`value`, `ms_per_step` and what describes them).  With --full, after the timed region (never inside it) the same process
+adds informative records to that line: the median of repeated blocks of the same K steps, in-pipeline times of every
+RegNetUS0 layer (`roofline_kernels`), the CPU baseline, and -- single GPU only -- configs[1] (c2, 288x216, D=192) and
+configs[2] (c3, ConvGRU sweep, 400x300, D=256) with their rates and their distance from the committed float64 fixtures
+(tests/golden/full_*.npz), the sessions and the training records.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (depth and probability maps) as float32
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -156,6 +161,20 @@ def cpu_baseline(workload, rp, budget_s=20.0, gpu_depth=None, max_maps=8):
                       "of the reference; TensorFlow reference not runnable offline) in %.1f s" % (n_done, w.name, el)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """--dump-outputs: `arrays` (name -> host array) as float32 DIR/<name>.npy; rank r > 0 writes <name>_rank<r>.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
+
+
 def rccl_version():
     try:
         v = torch.cuda.nccl.version()
@@ -204,10 +223,11 @@ def extra_config_3dcnn(name, dev, steps=10):
     return out
 
 
-def extra_config_gru(name, dev, steps=5, views=1):
+def extra_config_gru(name, dev, steps=5, views=1, outputs=None):
     """configs[2] (c3): the ConvGRU + winner-take-all sweep: rate, time per plane, agreement with its fixture.
     views > 1: that many independent reference views share the sweep's launches (mvs_gru_wta_batch_f32) -- how configuration 3
-    shards, ~135 reference views per GPU; view 0 is the fixture's reference view, the others differ in their features."""
+    shards, ~135 reference views per GPU; view 0 is the fixture's reference view, the others differ in their features.
+    outputs (a dict): receives the depth / prob maps (views, H, W) of the last timed sweep."""
     from mvsnet_amd import synthetic as S
     from mvsnet_amd.model import DepthPlan, MVSNetWeights, wta_depth_values
     w = S.make_workload(name)
@@ -226,6 +246,9 @@ def extra_config_gru(name, dev, steps=5, views=1):
     for i in range(2):
         step(i, False)
     el = timed_block(step, steps)
+    if outputs is not None:
+        outputs["depth"] = plan.depth_v[:views].cpu().numpy()
+        outputs["prob"] = plan.prob_v[:views].cpu().numpy()
     maps = steps * views
     flops = 2.0 * 23238 * w.depth_num * w.height * w.width          # 23 238 MAC per pixel and plane
     out = {"workload": "%s: N=%d, D=%d, %dx%d, ConvGRU sweep + winner-take-all, %d reference view(s) per sweep" % (
@@ -572,12 +595,20 @@ def main():
     ap.add_argument("--gru-views", type=int, default=1, help="reference views per recurrent sweep (--regularization GRU)")
     ap.add_argument("--extractor", choices=("hip", "torch"), default="hip", help="2D towers for --with-images")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the informative records (repeated blocks, two-stream pass, c2 / c3 configurations)")
-    ap.add_argument("--blocks", type=int, default=5, help="repeated blocks of --steps steps after the timed region")
-    ap.add_argument("--training-all", action="store_true", help="training record for D = 192 and the recurrent model too")
+                    help="with --full: skip the informative records (repeated blocks, two-stream pass, c2 / c3 configurations)")
+    ap.add_argument("--blocks", type=int, default=5, help="with --full: repeated blocks of --steps steps after the timed region")
+    ap.add_argument("--training-all", action="store_true", help="with --full: training record for D = 192 and the recurrent model too")
     ap.add_argument("--with-images", action="store_true",
                     help="also time images->depth (adds the PyTorch UNetDS2GN towers)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, the informative records too: roofline / per-layer passes, repeated blocks, towers, "
+                         "c2 / c3 / split-precision configurations, sessions, training, CPU baseline (--no-extra / "
+                         "--no-cpu-baseline trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the depth and probability maps of the last timed step as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly (`python bench.py --gpus N`, as the driver starts --gpus 1): this process stays GPU-less and
@@ -628,7 +659,10 @@ def main():
     cams = torch.as_tensor(w.cams).to(dev)
     if args.regularization == "GRU":
         # the recurrent sweep alone in this process (also how the 3D-CNN run obtains its `config_c3_gru` record)
-        rec = extra_config_gru(args.workload if args.workload != "M" else "c3", dev, args.steps, max(1, args.gru_views))
+        outputs = {} if args.dump_outputs else None
+        rec = extra_config_gru(args.workload if args.workload != "M" else "c3", dev, args.steps, max(1, args.gru_views), outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs, rank)
         print(json.dumps({"metric": "depth maps/sec (GRU regulariser)", "value": rec["depth_maps_per_s"], "unit": "depth maps/s",
                           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_depth_map"],
                           "dtype": "f32", "data": "synthetic", **rec}), flush=True)
@@ -664,10 +698,11 @@ def main():
         for i in range(10):
             step(i, False)
         torch.cuda.synchronize()
-    # the library brackets the dominant kernel (fused 3dconv0_1 + 3dconv1_0 pass) of every step of
-    # the timed region with HIP events on the stream it is launched on
+    # --full only: the library brackets the dominant kernel (fused 3dconv0_1 + 3dconv1_0 pass) of every step of the timed
+    # region with HIP events on the stream it is launched on (`roofline`); a plain run times the steps alone
     lib = _lib.load()
-    _lib.check(lib.mvs_profile_dominant(1), "mvs_profile_dominant")
+    if args.full:
+        _lib.check(lib.mvs_profile_dominant(1), "mvs_profile_dominant")
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -696,111 +731,54 @@ def main():
         every_dev = [None] * world
         dist.all_gather_object(every_dev, rank_devices[0])
         rank_devices = every_dev
-
-    import ctypes
-    pair_ms, pair_n = ctypes.c_double(0.0), ctypes.c_int(0)
-    _lib.check(lib.mvs_profile_dominant_ms(ctypes.byref(pair_ms), ctypes.byref(pair_n)), "mvs_profile_dominant_ms")
-    _lib.check(lib.mvs_profile_dominant(0), "mvs_profile_dominant")
-    # stage split (warp / conv stack / soft-argmin) for `roofline_kernels`: the SAME library call as the timed region, with the
-    # library's own event brackets between its stages (untimed pass -- every event record costs a microsecond or two of
-    # device idle time, and only the dominant kernel's bracket has to live inside the timed region)
-    stage_ms, stage_n = (ctypes.c_double * 3)(), ctypes.c_int(0)
-    _lib.check(lib.mvs_profile_stages(1), "mvs_profile_stages")
-    for i in range(min(args.steps, 20)):
-        step(i, True)
-    torch.cuda.synchronize()
-    _lib.check(lib.mvs_profile_stages_ms(stage_ms, ctypes.byref(stage_n)), "mvs_profile_stages_ms")
-    _lib.check(lib.mvs_profile_stages(0), "mvs_profile_stages")
-    t_warp, t_conv, t_soft = (max(stage_ms[k], 1e-6) * 1e-3 for k in range(3))      # [0] includes the tiny homography kernel
-    warp_bytes, conv_flops, soft_bytes = algorithmic_work(w.view_num, w.depth_num, w.height, w.width,
-                                                         w.channels, S.base_filter(args.network_mode))
+    # what the timed path returned in its last timed step (the plan of that step's stream)
+    last = plans[(args.steps - 1) % n_streams]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"depth": last.depth.cpu().numpy(), "prob": last.prob.cpu().numpy()}, rank)
     depth_np = plan.depth.cpu().numpy()
-    # every RegNetUS0 layer inside a depth map (untimed pass; the library brackets each launch with HIP events on the
-    # stream it goes to)
-    layer_ms = (ctypes.c_double * 11)()
-    layer_n = ctypes.c_int(0)
-    _lib.check(lib.mvs_profile_layers(1), "mvs_profile_layers")
-    for i in range(min(args.steps, 20)):
-        step(i, False)
-    torch.cuda.synchronize()
-    _lib.check(lib.mvs_profile_layers_ms(layer_ms, ctypes.byref(layer_n)), "mvs_profile_layers_ms")
-    _lib.check(lib.mvs_profile_layers(0), "mvs_profile_layers")
-    # the same K steps again, several times: the headline is one sample of a noisy quantity (clock ramps, DVFS)
+
     block_rates = []
-    if not args.no_extra and args.blocks > 0:
-        for _ in range(args.blocks):
-            if dist:
-                dist.barrier()
-            eb = timed_block(step, args.steps)
-            if dist:
-                tb = torch.tensor([eb], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
-                dist.all_reduce(tb, op=dist.ReduceOp.MAX)
-                eb = float(tb.item())
-            block_rates.append(world * args.steps / eb)
+    if args.full:
+        import ctypes
+        pair_ms, pair_n = ctypes.c_double(0.0), ctypes.c_int(0)
+        _lib.check(lib.mvs_profile_dominant_ms(ctypes.byref(pair_ms), ctypes.byref(pair_n)), "mvs_profile_dominant_ms")
+        _lib.check(lib.mvs_profile_dominant(0), "mvs_profile_dominant")
+        # stage split (warp / conv stack / soft-argmin) for `roofline_kernels`: the SAME library call as the timed region, with the
+        # library's own event brackets between its stages (untimed pass -- every event record costs a microsecond or two of
+        # device idle time, and only the dominant kernel's bracket has to live inside the timed region)
+        stage_ms, stage_n = (ctypes.c_double * 3)(), ctypes.c_int(0)
+        _lib.check(lib.mvs_profile_stages(1), "mvs_profile_stages")
+        for i in range(min(args.steps, 20)):
+            step(i, True)
+        torch.cuda.synchronize()
+        _lib.check(lib.mvs_profile_stages_ms(stage_ms, ctypes.byref(stage_n)), "mvs_profile_stages_ms")
+        _lib.check(lib.mvs_profile_stages(0), "mvs_profile_stages")
+        t_warp, t_conv, t_soft = (max(stage_ms[k], 1e-6) * 1e-3 for k in range(3))      # [0] includes the tiny homography kernel
+        warp_bytes, conv_flops, soft_bytes = algorithmic_work(w.view_num, w.depth_num, w.height, w.width,
+                                                             w.channels, S.base_filter(args.network_mode))
+        # every RegNetUS0 layer inside a depth map (untimed pass; the library brackets each launch with HIP events on the
+        # stream it goes to)
+        layer_ms = (ctypes.c_double * 11)()
+        layer_n = ctypes.c_int(0)
+        _lib.check(lib.mvs_profile_layers(1), "mvs_profile_layers")
+        for i in range(min(args.steps, 20)):
+            step(i, False)
+        torch.cuda.synchronize()
+        _lib.check(lib.mvs_profile_layers_ms(layer_ms, ctypes.byref(layer_n)), "mvs_profile_layers_ms")
+        _lib.check(lib.mvs_profile_layers(0), "mvs_profile_layers")
+        # the same K steps again, several times: the headline is one sample of a noisy quantity (clock ramps, DVFS)
+        if not args.no_extra and args.blocks > 0:
+            for _ in range(args.blocks):
+                if dist:
+                    dist.barrier()
+                eb = timed_block(step, args.steps)
+                if dist:
+                    tb = torch.tensor([eb], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
+                    dist.all_reduce(tb, op=dist.ReduceOp.MAX)
+                    eb = float(tb.item())
+                block_rates.append(world * args.steps / eb)
 
     if rank == 0:
-        tr = pmc_traffic()
-        kernels = [
-            # Priced against HBM (its floor: the volume's write), but NOT HBM-bound: the kernel is bound by instruction issue --
-            # vector ALU + vector-memory (TA) instructions at 4 waves per SIMD (counters below: SQ_ACTIVE_INST_ANY of the four
-            # waves of a SIMD adds up to ~0.9 of the kernel's duration, TA busy ~0.74 of it, HBM traffic = 1.00 x algorithmic).
-            # Four other forms were built and measured no faster (LDS-staged, MFMA blend x 2, parity-slot tap cache).
-            {"kernel": "warp+variance cost volume (cost_volume_sweep_kernel)", "bound": "valu+ta",
-             "achieved": warp_bytes / t_warp / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-             "frac": warp_bytes / t_warp / 1e9 / HBM_PEAK_GBS, "ms": t_warp * 1e3,
-             "frac_is": "fraction of the HBM peak (the kernel's floor); the binding resource is instruction issue, see counters",
-             "algorithmic_bytes": warp_bytes, "traffic": tr.get("warp") or None, "counters": tr.get("warp_counters")},
-            {"kernel": "RegNetUS0 3D conv stack (11 conv launches, BatchNorm folded into the consumers)", "bound": "mfma",
-             "achieved": conv_flops / t_conv / 1e12, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-             "frac": conv_flops / t_conv / 1e12 / MFMA_F32_PEAK_TFLOPS, "ms": t_conv * 1e3,
-             "algorithmic_flops": conv_flops, "peak_dtype": "fp32-input MFMA (dense)",
-             "traffic": tr.get("conv") or None},
-            {"kernel": "softmax+soft-argmin+prob (softargmin_prob_kernel)", "bound": "hbm",
-             "achieved": soft_bytes / t_soft / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-             "frac": soft_bytes / t_soft / 1e9 / HBM_PEAK_GBS, "ms": t_soft * 1e3,
-             "algorithmic_bytes": soft_bytes, "traffic": tr.get("soft") or None},
-        ]
-        # The dominant KERNEL (one launch): conv3d_c8_kernel, the fused pass of 3dconv0_1 (32->8, stride 1)
-        # and 3dconv1_0 (32->16, stride 2) over the cost volume: 27*32*(8 + 16/8) MAC per full-resolution voxel.
-        if pair_n.value > 0 and w.channels == 32 and S.base_filter(args.network_mode) == 8 and args.conv_impl in ("auto", "mfma"):
-            pair_flops = 2.0 * 27 * 32 * (8 + 16 / 8.0) * w.depth_num * w.height * w.width
-            t_pair = pair_ms.value * 1e-3
-            kernels.append({"kernel": "conv3d_c8_kernel<true,false>: fused 3dconv0_1 + 3dconv1_0 pass over the cost volume (one launch)",
-                            "bound": "mfma", "achieved": pair_flops / t_pair / 1e12, "peak": MFMA_F32_PEAK_TFLOPS,
-                            "unit": "TFLOP/s", "frac": pair_flops / t_pair / 1e12 / MFMA_F32_PEAK_TFLOPS,
-                            "ms": t_pair * 1e3, "algorithmic_flops": pair_flops, "launches_timed": pair_n.value,
-                            "peak_dtype": "fp32-input MFMA (dense)", "traffic": tr.get("pair") or None})
-            dominant = kernels[-1]
-        else:
-            dominant = max(kernels, key=lambda k: k["ms"])
-        if layer_n.value > 0:
-            lf = layer_flops(w.channels, S.base_filter(args.network_mode), w.depth_num * w.height * w.width)
-            fused = layer_ms[LAYERS.index("3dconv1_0")] == 0.0 and layer_ms[LAYERS.index("3dconv0_1")] > 0.0
-            fused2 = layer_ms[LAYERS.index("3dconv2_0")] == 0.0 and layer_ms[LAYERS.index("3dconv1_1")] > 0.0      # round 4: 3dconv2_0 rides in 3dconv1_1's launch
-            # round 4: 3dconv2_1's blocks ride as fillers in the launches of 3dconv3_0 / 3_1 / 4_0 (no launch of its own)
-            shares = (ctypes.c_int * 3)()
-            _lib.check(lib.mvs_regnet_filler_shares(shares), "mvs_regnet_filler_shares")
-            filled = layer_ms[LAYERS.index("3dconv2_1")] == 0.0 and layer_ms[LAYERS.index("3dconv3_1")] > 0.0 and sum(shares) == 1000
-            share_of = dict(zip(("3dconv3_0", "3dconv3_1", "3dconv4_0"), (x / 1000.0 for x in shares))) if filled else {}
-            for li, name in enumerate(LAYERS):
-                ms = layer_ms[li]
-                if ms <= 0.0:
-                    continue
-                rider = "3dconv1_0" if (fused and name == "3dconv0_1") else "3dconv2_0" if (fused2 and name == "3dconv1_1") else None
-                fl = lf[name] + (lf[rider] if rider else 0.0) + share_of.get(name, 0.0) * lf["3dconv2_1"]
-                label = name + (" + %s fused" % rider if rider else "")
-                if name in share_of:
-                    label += " + %.2f of 3dconv2_1's blocks as filler workgroups" % share_of[name]
-                row = {"kernel": "%s (in-pipeline, HIP events around the launch)" % label,
-                       "ms": ms, "algorithmic_flops": fl, "launches_timed": layer_n.value}
-                if name == "3dconv6_2":                     # 8 -> 1 channels: reads two 8-channel volumes, writes one channel
-                    by = w.depth_num * w.height * w.width * (2 * 8 + 1) * 4
-                    row.update({"bound": "hbm", "achieved": by / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                "frac": by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes": by})
-                else:
-                    row.update({"bound": "mfma", "achieved": fl / (ms * 1e-3) / 1e12, "peak": MFMA_F32_PEAK_TFLOPS,
-                                "unit": "TFLOP/s", "frac": fl / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS})
-                kernels.append(row)
         out = {
             "metric": "depth maps/sec (N=5, D=192, 160x128)" if args.workload == "M" else "depth maps/sec",
             "value": world * args.steps / elapsed,
@@ -816,31 +794,96 @@ def main():
                                        w.name, w.view_num, w.depth_num, w.width, w.height, w.channels,
                                        args.network_mode),
                        "conv_impl": args.conv_impl, "streams_per_gpu": n_streams},
-            "roofline": {k: dominant[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")},
-            "roofline_kernels": kernels,
-            "roofline_stage_rows": {"sum_ms": (t_warp + t_conv + t_soft) * 1e3, "ms_per_step": elapsed / args.steps * 1e3,
-                                    "launches_timed": stage_n.value,
-                                    "source": "the first three rows of roofline_kernels are the library's own HIP-event brackets between the stages of "
-                                              "mvs_depth_from_features_f32 (mvs_profile_stages), i.e. of the timed path; their sum exceeds ms_per_step "
-                                              "by the device idle time of four event records per depth map"},
             "depth_checksum": float(np.float64(depth_np).sum()),
             "per_rank_depth_maps_per_s": {"min": min(rank_rates), "max": max(rank_rates), "ranks": rank_rates},
             "ranks": {"world_size": dist.get_world_size() if dist else 1, "backend": (backend + (" (RCCL)" if backend == "nccl" else "")) if dist else None,
                       "rccl_version": rccl_version(), "distinct_pci_bus_ids": len({d_.get("pci_bus_id") for d_ in rank_devices}),
                       "devices": rank_devices},
         }
-        chain = ["3dconv2_0", "3dconv3_0", "3dconv3_1", "3dconv4_0", "3dconv5_0"]
-        if layer_n.value > 0:
-            out["low_resolution_chain_us"] = 1e3 * sum(layer_ms[LAYERS.index(n_)] for n_ in chain)     # (3dconv2_0 counts 0 when it rides in 3dconv1_1's launch)
-            if layer_ms[LAYERS.index("3dconv2_1")] == 0.0:
-                out["low_resolution_chain_includes"] = "3dconv2_1 (its blocks ride in the launches of 3dconv3_0 / 3_1 / 4_0)"
-        if block_rates:
-            out["repeat_blocks"] = {"blocks": len(block_rates), "steps_per_block": args.steps,
-                                    "median": float(np.median(block_rates)), "min": min(block_rates), "max": max(block_rates),
-                                    "values": block_rates}
-        out["roofline"]["kernel"] = dominant["kernel"]
-        out["roofline"]["traffic_source"] = tr.get("source")
-        if args.with_images or (world == 1 and n_streams == 1 and not args.no_extra and args.workload == "M" and args.extractor == "hip"):
+        if args.full:
+            tr = pmc_traffic()
+            kernels = [
+                # Priced against HBM (its floor: the volume's write), but NOT HBM-bound: the kernel is bound by instruction issue --
+                # vector ALU + vector-memory (TA) instructions at 4 waves per SIMD (counters below: SQ_ACTIVE_INST_ANY of the four
+                # waves of a SIMD adds up to ~0.9 of the kernel's duration, TA busy ~0.74 of it, HBM traffic = 1.00 x algorithmic).
+                # Four other forms were built and measured no faster (LDS-staged, MFMA blend x 2, parity-slot tap cache).
+                {"kernel": "warp+variance cost volume (cost_volume_sweep_kernel)", "bound": "valu+ta",
+                 "achieved": warp_bytes / t_warp / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                 "frac": warp_bytes / t_warp / 1e9 / HBM_PEAK_GBS, "ms": t_warp * 1e3,
+                 "frac_is": "fraction of the HBM peak (the kernel's floor); the binding resource is instruction issue, see counters",
+                 "algorithmic_bytes": warp_bytes, "traffic": tr.get("warp") or None, "counters": tr.get("warp_counters")},
+                {"kernel": "RegNetUS0 3D conv stack (11 conv launches, BatchNorm folded into the consumers)", "bound": "mfma",
+                 "achieved": conv_flops / t_conv / 1e12, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                 "frac": conv_flops / t_conv / 1e12 / MFMA_F32_PEAK_TFLOPS, "ms": t_conv * 1e3,
+                 "algorithmic_flops": conv_flops, "peak_dtype": "fp32-input MFMA (dense)",
+                 "traffic": tr.get("conv") or None},
+                {"kernel": "softmax+soft-argmin+prob (softargmin_prob_kernel)", "bound": "hbm",
+                 "achieved": soft_bytes / t_soft / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                 "frac": soft_bytes / t_soft / 1e9 / HBM_PEAK_GBS, "ms": t_soft * 1e3,
+                 "algorithmic_bytes": soft_bytes, "traffic": tr.get("soft") or None},
+            ]
+            # The dominant KERNEL (one launch): conv3d_c8_kernel, the fused pass of 3dconv0_1 (32->8, stride 1)
+            # and 3dconv1_0 (32->16, stride 2) over the cost volume: 27*32*(8 + 16/8) MAC per full-resolution voxel.
+            if pair_n.value > 0 and w.channels == 32 and S.base_filter(args.network_mode) == 8 and args.conv_impl in ("auto", "mfma"):
+                pair_flops = 2.0 * 27 * 32 * (8 + 16 / 8.0) * w.depth_num * w.height * w.width
+                t_pair = pair_ms.value * 1e-3
+                kernels.append({"kernel": "conv3d_c8_kernel<true,false>: fused 3dconv0_1 + 3dconv1_0 pass over the cost volume (one launch)",
+                                "bound": "mfma", "achieved": pair_flops / t_pair / 1e12, "peak": MFMA_F32_PEAK_TFLOPS,
+                                "unit": "TFLOP/s", "frac": pair_flops / t_pair / 1e12 / MFMA_F32_PEAK_TFLOPS,
+                                "ms": t_pair * 1e3, "algorithmic_flops": pair_flops, "launches_timed": pair_n.value,
+                                "peak_dtype": "fp32-input MFMA (dense)", "traffic": tr.get("pair") or None})
+                dominant = kernels[-1]
+            else:
+                dominant = max(kernels, key=lambda k: k["ms"])
+            if layer_n.value > 0:
+                lf = layer_flops(w.channels, S.base_filter(args.network_mode), w.depth_num * w.height * w.width)
+                fused = layer_ms[LAYERS.index("3dconv1_0")] == 0.0 and layer_ms[LAYERS.index("3dconv0_1")] > 0.0
+                fused2 = layer_ms[LAYERS.index("3dconv2_0")] == 0.0 and layer_ms[LAYERS.index("3dconv1_1")] > 0.0      # round 4: 3dconv2_0 rides in 3dconv1_1's launch
+                # round 4: 3dconv2_1's blocks ride as fillers in the launches of 3dconv3_0 / 3_1 / 4_0 (no launch of its own)
+                shares = (ctypes.c_int * 3)()
+                _lib.check(lib.mvs_regnet_filler_shares(shares), "mvs_regnet_filler_shares")
+                filled = layer_ms[LAYERS.index("3dconv2_1")] == 0.0 and layer_ms[LAYERS.index("3dconv3_1")] > 0.0 and sum(shares) == 1000
+                share_of = dict(zip(("3dconv3_0", "3dconv3_1", "3dconv4_0"), (x / 1000.0 for x in shares))) if filled else {}
+                for li, name in enumerate(LAYERS):
+                    ms = layer_ms[li]
+                    if ms <= 0.0:
+                        continue
+                    rider = "3dconv1_0" if (fused and name == "3dconv0_1") else "3dconv2_0" if (fused2 and name == "3dconv1_1") else None
+                    fl = lf[name] + (lf[rider] if rider else 0.0) + share_of.get(name, 0.0) * lf["3dconv2_1"]
+                    label = name + (" + %s fused" % rider if rider else "")
+                    if name in share_of:
+                        label += " + %.2f of 3dconv2_1's blocks as filler workgroups" % share_of[name]
+                    row = {"kernel": "%s (in-pipeline, HIP events around the launch)" % label,
+                           "ms": ms, "algorithmic_flops": fl, "launches_timed": layer_n.value}
+                    if name == "3dconv6_2":                     # 8 -> 1 channels: reads two 8-channel volumes, writes one channel
+                        by = w.depth_num * w.height * w.width * (2 * 8 + 1) * 4
+                        row.update({"bound": "hbm", "achieved": by / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                    "frac": by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes": by})
+                    else:
+                        row.update({"bound": "mfma", "achieved": fl / (ms * 1e-3) / 1e12, "peak": MFMA_F32_PEAK_TFLOPS,
+                                    "unit": "TFLOP/s", "frac": fl / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS})
+                    kernels.append(row)
+            out.update({
+                "roofline": {k: dominant[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")},
+                "roofline_kernels": kernels,
+                "roofline_stage_rows": {"sum_ms": (t_warp + t_conv + t_soft) * 1e3, "ms_per_step": elapsed / args.steps * 1e3,
+                                        "launches_timed": stage_n.value,
+                                        "source": "the first three rows of roofline_kernels are the library's own HIP-event brackets between the stages of "
+                                                  "mvs_depth_from_features_f32 (mvs_profile_stages), i.e. of the timed path; their sum exceeds ms_per_step "
+                                                  "by the device idle time of four event records per depth map"},
+            })
+            chain = ["3dconv2_0", "3dconv3_0", "3dconv3_1", "3dconv4_0", "3dconv5_0"]
+            if layer_n.value > 0:
+                out["low_resolution_chain_us"] = 1e3 * sum(layer_ms[LAYERS.index(n_)] for n_ in chain)     # (3dconv2_0 counts 0 when it rides in 3dconv1_1's launch)
+                if layer_ms[LAYERS.index("3dconv2_1")] == 0.0:
+                    out["low_resolution_chain_includes"] = "3dconv2_1 (its blocks ride in the launches of 3dconv3_0 / 3_1 / 4_0)"
+            if block_rates:
+                out["repeat_blocks"] = {"blocks": len(block_rates), "steps_per_block": args.steps,
+                                        "median": float(np.median(block_rates)), "min": min(block_rates), "max": max(block_rates),
+                                        "values": block_rates}
+            out["roofline"]["kernel"] = dominant["kernel"]
+            out["roofline"]["traffic_source"] = tr.get("source")
+        if args.with_images or (args.full and world == 1 and n_streams == 1 and not args.no_extra and args.workload == "M" and args.extractor == "hip"):
             up = S.make_unet_params(args.network_mode, seed=3)
             if args.extractor == "hip":
                 from mvsnet_amd.feature_net_hip import HipUNetDS2GN as UNetDS2GN
@@ -908,7 +951,7 @@ def main():
                 piped(args.steps)
                 torch.cuda.synchronize()
                 out["images_to_depth_maps_per_s_towers_on_their_own_stream"] = args.steps / (time.perf_counter() - t1)
-        if world == 1 and n_streams == 1 and not args.no_extra and args.workload == "M" and args.network_mode == "normal":
+        if args.full and world == 1 and n_streams == 1 and not args.no_extra and args.workload == "M" and args.network_mode == "normal":
             # BASELINE.json configs[1] and configs[2] on this GPU, each with its distance from the committed fixture
             t_x = [time.perf_counter()]
 
@@ -948,7 +991,7 @@ def main():
             out["training"] = training_record(dev, configs=(("3dcnn_d192", "3DCNN", 192), ("3dcnn_d128_config5", "3DCNN", 128), ("gru_d192", "GRU", 192))
                                               if args.training_all else (("3dcnn_d128_config5", "3DCNN", 128),)); lap("training")
             out["training_from_disk"] = training_from_disk_record(); lap("training_from_disk")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w, rp, args.cpu_budget, depth_np)
             if args.workload == "M":       # configs[0]: the configuration BASELINE.json defines AS the CPU run (N=3, D=32, 160x128 features)
                 w1 = S.make_workload("c1", args.network_mode, seed=0)

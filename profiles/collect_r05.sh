@@ -29,7 +29,7 @@ ls -la gpurun_out/r05/r05*
 # SQ counters of the 4-view recurrent sweep, per kernel and plane
 bash tools/gru_pmc.sh > gpurun_out/r05/r05_gru_pmc_B4.txt 2>&1
 # the default bench record of the round (what the driver runs)
-timeout -k 10 600 python bench.py > gpurun_out/r05/r05_bench_default.json 2> gpurun_out/r05/r05_bench_default.err
+timeout -k 10 600 python bench.py --full > $OUT/r05_bench_default.json 2> $OUT/r05_bench_default.err
 ls -la gpurun_out/r05/r05*
 # round 5: device-side time line of the fused recurrent sweep, the probes behind its design, the capture reproducer
 for B in 1 4; do timeout -k 10 200 python tools/gru_fused_trace.py --views $B 2>&1 | grep -A1 launch; done > gpurun_out/r05/r05_gru_fused_trace.txt

@@ -14,5 +14,5 @@ python profiles/summarize.py $OUT gpurun_out/r06/r06
 UNET_SIDE=0 bash tools/r6_unet_counters.sh > $OUT/unet_counters.log 2>&1
 cp gpurun_out/r06_unet/table.txt $OUT/r06_unet_counters_after.txt
 # the default bench record of the round (what the driver runs)
-timeout -k 10 900 python bench.py > $OUT/r06_bench_default.json 2> $OUT/r06_bench_default.err
+timeout -k 10 900 python bench.py --full > $OUT/r06_bench_default.json 2> $OUT/r06_bench_default.err
 ls -la $OUT/r06*

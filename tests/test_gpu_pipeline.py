@@ -373,7 +373,7 @@ def test_bench_and_inference_start_their_own_ranks(tmp_path, lib_built):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--full", "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     rec = json.loads(line)
@@ -407,6 +407,42 @@ def test_bench_and_inference_start_their_own_ranks(tmp_path, lib_built):
     for i in range(5):                                     # same files as the two-rank run above
         a = open(os.path.join(out, "%d_init.pfm" % i), "rb").read()
         assert a == open(os.path.join(out2, "%d_init.pfm" % i), "rb").read()
+
+
+def test_plain_bench_times_the_requested_steps_and_dumps_the_last_outputs(tmp_path, lib_built):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line alone, and --dump-outputs writes the depth /
+    probability maps of the last timed step as float32 .npy, the same in two runs (seeded inputs) and the library's own call
+    on those inputs."""
+    import json
+    import subprocess
+    import sys
+    from mvsnet_amd.model import DepthPlan, MVSNetWeights
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    recs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--workload", "small", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec["steps"] == 7 and rec["warmup"] == 2 and rec["n_gpus"] == 1
+        assert rec["unit"] == "depth maps/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]
+        assert not {"roofline", "roofline_kernels", "repeat_blocks", "cpu_baseline", "config_c2", "training"} & set(rec)
+    w = S.make_workload("small", "normal", seed=0)
+    weights = MVSNetWeights.from_numpy("normal", regnet=S.make_regnet_params("normal", seed=1), device=DEV)
+    plan = DepthPlan(w.view_num, w.depth_num, w.height, w.width, w.channels, weights, "3DCNN", DEV)
+    depth, prob = plan.run_depth(t(w.features), t(w.cams), w.depth_start, w.depth_interval, w.depth_end, False)
+    want = {"depth": depth.cpu().numpy(), "prob": prob.cpu().numpy()}
+    for name in ("depth", "prob"):
+        a, b = (np.load(str(tmp_path / run / (name + ".npy"))) for run in ("a", "b"))
+        assert a.dtype == np.float32 and a.shape == (w.height, w.width)
+        np.testing.assert_allclose(a, b, rtol=1e-6, atol=1e-7)
+        np.testing.assert_allclose(a, want[name], rtol=1e-5, atol=1e-6)
 
 
 def test_bench_with_four_ranks_on_one_card_and_a_failing_rank(lib_built):
