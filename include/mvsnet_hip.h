@@ -570,6 +570,30 @@ size_t mvs_conv2d_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout);
 int mvs_conv2d_wgrad_f32(const float* x, const float* g, int g_stride, int g_off, int N, int H, int W, int Cin,
                          int Cout, void* workspace, size_t workspace_bytes, float* dw, void* stream);
 
+/* Geometric-consistency fusion of V depth maps into one coloured point cloud (csrc/fusion.hip; replaces the external
+ * fusibile run of mvsnet/depthfusion.py:194-214 with this project's own algorithm, specified in mvsnet_amd/fusion.py --
+ * not bit-compatible with fusibile):
+ *   depth, prob   (V,H,W) float32; a pixel is valid when depth > 0, finite and prob >= prob_threshold
+ *   tables        V*V*12 + V*12 floats: M[a][b] (3x4, row-major) = P_b o B_a at [(a*V + b)*12], then B_v at [V*V*12 + v*12];
+ *                 B_v maps (x d, y d, d, 1) of view v's pixel (x, y) at depth d to the world point, P_b = K_b [R_b | t_b]
+ *   src_offsets   V+1 int32, src_index: view r's sources are src_index[src_offsets[r] .. src_offsets[r+1]), ascending,
+ *                 r itself excluded (entries out of range or equal to r are skipped); at most max_sources are used per view
+ *   num_consistent  a pixel is kept when its count of consistent sources n >= num_consistent (compared as float)
+ *   dedupe        1: views in ascending order, witnesses of kept pixels are never reference pixels later; 0: views independent
+ *   images        (V,img_h,img_w,3) uint8 or NULL (colours 0); nearest pixel ((x+1/2) img_w / W, (y+1/2) img_h / H)
+ *   xyz (V*H*W,3) float32, rgb (V*H*W,3) uint8, view_index (V*H*W) int32, pixel_index (V*H*W) int32 or NULL (row-major
+ *                 y*W + x of the point's reference pixel): capacity for every pixel; the first *count entries (count: one
+ *                 int32 on the device) are the points, by view ascending then row-major pixel order
+ *   workspace     mvs_fusion_workspace_bytes(V, H, W, max_sources, dedupe) bytes (MVS_E_WORKSPACE when smaller)
+ * Deterministic: integer counts and fixed-order float32 sums, no float atomics (two runs give the same bytes).
+ * MVS_E_SHAPE when V*H*W exceeds 2^31-1 or V or max_sources exceeds 65535. */
+size_t mvs_fusion_workspace_bytes(int V, int H, int W, int max_sources, int dedupe);
+int mvs_fusion_f32(const float* depth, const float* prob, int V, int H, int W, const float* tables, const int* src_offsets,
+                   const int* src_index, int max_sources, float prob_threshold, float reproj_threshold,
+                   float depth_rel_threshold, float num_consistent, int dedupe, const uint8_t* images, int img_h, int img_w,
+                   float* xyz, uint8_t* rgb, int* view_index, int* pixel_index, int* count, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

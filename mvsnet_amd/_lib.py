@@ -106,6 +106,8 @@ SIGNATURES = {
     "mvs_gru_release": (_i, [_p]),
     "mvs_gru_stream_layout": (_i, [_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "mvs_regnet_filler_shares": (_i, [C.POINTER(C.c_int)]),
+    "mvs_fusion_workspace_bytes": (_sz, [_i] * 5),
+    "mvs_fusion_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}

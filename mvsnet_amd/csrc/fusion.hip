@@ -1,0 +1,374 @@
+// Geometric-consistency fusion of a session's depth maps into one coloured point cloud (the step the
+// reference hands to the external CUDA program fusibile, mvsnet/depthfusion.py:194-214).  The algorithm is this project's own
+// and fully specified in mvsnet_amd/fusion.py; it is NOT bit-compatible with fusibile (no disparity criterion, no normals).
+//
+// Per reference pixel p = (x, y) of view r with filtered depth d > 0 and every source s of r's list (ascending):
+//   (u, v, w)    = M[r][s] (x d, y d, d, 1)          project into s; w > 0
+//   q            = (floor(u/w + 1/2), floor(v/w + 1/2)) inside s and valid there (filtered depth ds > 0)
+//   (u', v', w') = M[s][r] (qx ds, qy ds, ds, 1)     back into r; w' > 0
+//   consistent   : |(u'/w', v'/w') - (x, y)|^2 < reproj^2 and |w' - d| < depth_rel d
+// M[a][b] = P_b o B_a (3x4, float32 on the device, composed in float64 on the host): B_a maps (x d, y d, d, 1) to the world
+// point, P_b = K_b [R_b | t_b].  A (pixel, source) pair is two 3x4 products, two IEEE reciprocals and one gather of the
+// source's filtered depth; a consistent pair adds a third 3x4 product (its world point).
+//
+// Launches (all on the caller's stream; nothing allocated, nothing synchronised -- the whole call captures into a hipGraph):
+//   filter    df = D where D > 0, finite and P >= prob_threshold, else 0 (all views; the gathers read df only);
+//   pairs     one lane per reference pixel, the wave's sources a contiguous chunk ("slice") of r's list: source indices and
+//             table entries are wave-uniform scalar loads (constant address space + readfirstlane; checked in the ISA).  Per
+//             slice a partial sum of (X_s - X) and the consistent count, SoA planes;
+//   finalize  slices summed in slice order (fixed: results are bitwise reproducible), keep = n >= num_consistent, fused point
+//             X + sum / (n + 1); in dedupe mode the witnesses q of a kept pixel are marked used (uint8 stores of 1);
+//   compact   per-1024-pixel counts, one exclusive scan, ordered writes: view ascending, then row-major pixel order.
+// dedupe = 0: pairs + finalize once over all views.  dedupe = 1: views in ascending order, pairs + finalize per view (the marks
+// of view r land only in views != r, so a view's pixels run in parallel); its 20 480 pixels at 160 x 128 are 320 waves, so the
+// sources of a pixel are spread over up to 16 slices (grid.z) to fill the 256 CUs.
+// The compiler merges some neighbouring stores into wide ones; tools/store_hazard_scan.py (run by the CPU suite) finds none of
+// them with its data registers overwritten too early.
+#include "common.h"
+
+namespace {
+
+constexpr int FU_THREADS = 256;
+constexpr int FU_TABLE = 12;          // floats per 3x4 matrix
+constexpr int FU_MAX_SLICES = 16;
+constexpr int FU_CHUNK = 1024;        // pixels per compaction block (4 per thread)
+
+__global__ __launch_bounds__(FU_THREADS) void fusion_filter_kernel(const float* __restrict__ depth, const float* __restrict__ prob,
+                                                                    size_t n, float thr, float* __restrict__ df) {
+    const size_t i = (size_t)blockIdx.x * FU_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float d = depth[i], p = prob[i];
+    df[i] = (d > 0.f && __builtin_isfinite(d) && p >= thr) ? d : 0.f;
+}
+
+__device__ __forceinline__ void fu_apply(const float* __restrict__ m, float a0, float a1, float a2, float& o0, float& o1, float& o2) {
+    o0 = fmaf(m[0], a0, fmaf(m[1], a1, fmaf(m[2], a2, m[3])));
+    o1 = fmaf(m[4], a0, fmaf(m[5], a1, fmaf(m[6], a2, m[7])));
+    o2 = fmaf(m[8], a0, fmaf(m[9], a1, fmaf(m[10], a2, m[11])));
+}
+
+// Wave-uniform, read-only data through the scalar unit: a load from the constant address space at a uniform address is an
+// s_load (a plain global pointer would be loaded per lane: the compiler cannot prove the memory unclobbered).
+typedef __attribute__((address_space(4))) const float fu_cfloat;
+typedef __attribute__((address_space(4))) const int fu_cint;
+
+struct FuMat { float m[FU_TABLE]; };
+
+// Matrix `index` (wave-uniform; readfirstlane states it to the compiler) of a table of 3x4 matrices.
+__device__ __forceinline__ FuMat fu_load_mat(const float* table, int index) {
+    const fu_cfloat* c = (const fu_cfloat*)table + (size_t)__builtin_amdgcn_readfirstlane(index) * FU_TABLE;
+    FuMat t;
+#pragma unroll
+    for (int i = 0; i < FU_TABLE; ++i) t.m[i] = c[i];
+    return t;
+}
+
+// Ties the loaded values to this point in the program: the compiler cannot sink the scalar loads into the (divergent)
+// branches that use them, so a whole iteration's tables arrive in one round trip.
+__device__ __forceinline__ void fu_pin(const FuMat& t) {
+#pragma unroll
+    for (int i = 0; i < FU_TABLE; ++i) asm volatile("" ::"s"(t.m[i]));
+}
+
+__device__ __forceinline__ int fu_load_uniform(const int* p, int i) {
+    return ((const fu_cint*)p)[__builtin_amdgcn_readfirstlane(i)];
+}
+
+// grid (cdiv(HW, 256), views of this launch, slices).  part: (slices, 4, nview, HW) floats = sum of (X_s - X) x/y/z, count.
+// witness (dedupe only): (max_src, HW) int32, view * HW + q of the consistent source at list position j, else -1.
+// The reference view r, its source list and the source s of an iteration are wave-uniform (they depend on blockIdx and the
+// loop counter only): the list and the three 3x4 tables of a pair (M[r][s], M[s][r], B_s) are scalar loads, one iteration
+// ahead.  The only vector-memory access of an iteration is the gather of the source's filtered depth (plus the witness store
+// in dedupe mode).
+__global__ __launch_bounds__(FU_THREADS) void fusion_pairs_kernel(
+        const float* __restrict__ df, const uint8_t* used, const float* __restrict__ M, const float* __restrict__ B,
+        const int* __restrict__ src_off, const int* __restrict__ src_idx, int max_src, int V, int H, int W, int v0, int chunk,
+        float reproj2, float depth_rel, float* __restrict__ part, int* __restrict__ witness) {
+    const int HW = H * W;
+    const int vl = blockIdx.y, r = v0 + vl, nview = gridDim.y;
+    const int slice = blockIdx.z;
+    const int p = blockIdx.x * FU_THREADS + threadIdx.x;
+    const bool inside = p < HW;
+    const int x = inside ? p % W : 0, y = inside ? p / W : 0;
+    float d = inside ? df[(size_t)r * HW + p] : 0.f;
+    if (used && inside && used[(size_t)r * HW + p]) d = 0.f;
+    const bool ref = d > 0.f;
+    const int beg = fu_load_uniform(src_off, r);
+    int cnt = fu_load_uniform(src_off, r + 1) - beg;
+    cnt = cnt < 0 ? 0 : (cnt > max_src ? max_src : cnt);
+    const int j0 = min(slice * chunk, cnt), j1 = min(j0 + chunk, cnt);
+    const float fx = (float)x, fy = (float)y;
+    const float a0 = fx * d, a1 = fy * d;
+    float X0, X1, X2;
+    const FuMat Br = fu_load_mat(B, r);
+    fu_apply(Br.m, a0, a1, d, X0, X1, X2);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, n = 0.f;
+    // one-iteration software pipeline: the tables of source j+1 and the index of source j+2 are requested at the top of
+    // iteration j and waited for at its bottom, so an iteration waits on its own gather only.  An out-of-range source
+    // loads view r's tables instead (never used) so that every address stays inside the tables.
+    const auto safe = [&](int src) { return (src >= 0 && src < V) ? src : r; };
+    int s_cur = j0 < j1 ? fu_load_uniform(src_idx, beg + j0) : r;
+    int s_nxt = j0 + 1 < j1 ? fu_load_uniform(src_idx, beg + j0 + 1) : s_cur;
+    FuMat Mrs = fu_load_mat(M, r * V + safe(s_cur)), Msr = fu_load_mat(M, safe(s_cur) * V + r), Bs = fu_load_mat(B, safe(s_cur));
+    fu_pin(Mrs); fu_pin(Msr); fu_pin(Bs);
+    for (int j = j0; j < j1; ++j) {
+        const int s = s_cur, sn = s_nxt;
+        const FuMat nMrs = fu_load_mat(M, r * V + safe(sn)), nMsr = fu_load_mat(M, safe(sn) * V + r), nBs = fu_load_mat(B, safe(sn));
+        const int snn = j + 2 < j1 ? fu_load_uniform(src_idx, beg + j + 2) : sn;
+        int wit = -1;
+        if (s >= 0 && s < V && s != r) {                  // uniform branch
+            float u, v, w;
+            fu_apply(Mrs.m, a0, a1, d, u, v, w);
+            if (ref && w > 0.f) {
+                const float iw = 1.0f / w;
+                const float qxf = floorf(u * iw + 0.5f), qyf = floorf(v * iw + 0.5f);
+                if (qxf >= 0.f && qxf < (float)W && qyf >= 0.f && qyf < (float)H) {
+                    const int q = (int)qyf * W + (int)qxf;
+                    const float ds = df[(size_t)s * HW + q];
+                    if (ds > 0.f) {
+                        const float b0 = qxf * ds, b1 = qyf * ds;
+                        float u2, v2, w2;
+                        fu_apply(Msr.m, b0, b1, ds, u2, v2, w2);
+                        if (w2 > 0.f) {
+                            const float iw2 = 1.0f / w2;
+                            const float ex = u2 * iw2 - fx, ey = v2 * iw2 - fy;
+                            if (ex * ex + ey * ey < reproj2 && fabsf(w2 - d) < depth_rel * d) {
+                                float Y0, Y1, Y2;
+                                fu_apply(Bs.m, b0, b1, ds, Y0, Y1, Y2);
+                                s0 += Y0 - X0; s1 += Y1 - X1; s2 += Y2 - X2; n += 1.f;
+                                wit = s * HW + q;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (witness && inside) witness[(size_t)j * HW + p] = wit;
+        fu_pin(nMrs); fu_pin(nMsr); fu_pin(nBs);
+        Mrs = nMrs; Msr = nMsr; Bs = nBs;
+        s_cur = sn; s_nxt = snn;
+    }
+    if (!inside) return;
+    const size_t plane = (size_t)nview * HW, base = (size_t)slice * 4 * plane + (size_t)vl * HW + p;
+    part[base] = s0;
+    part[base + plane] = s1;
+    part[base + 2 * plane] = s2;
+    part[base + 3 * plane] = n;
+}
+
+// grid (cdiv(HW, 256), views of this launch).  keep (V, HW) uint8, fxyz (V, HW, 3) float32.
+__global__ __launch_bounds__(FU_THREADS) void fusion_finalize_kernel(
+        const float* __restrict__ df, uint8_t* used, const float* __restrict__ B, const float* __restrict__ part, int slices,
+        const int* __restrict__ src_off, const int* __restrict__ witness, int max_src, int H, int W, int v0, float num_consistent,
+        uint8_t* __restrict__ keep, float* __restrict__ fxyz) {
+    const int HW = H * W;
+    const int vl = blockIdx.y, r = v0 + vl, nview = gridDim.y;
+    const int p = blockIdx.x * FU_THREADS + threadIdx.x;
+    if (p >= HW) return;
+    const size_t e = (size_t)r * HW + p;
+    float d = df[e];
+    if (used && used[e]) d = 0.f;
+    const float fx = (float)(p % W), fy = (float)(p / W);
+    float X0, X1, X2;
+    fu_apply(B + (size_t)r * FU_TABLE, fx * d, fy * d, d, X0, X1, X2);
+    const size_t plane = (size_t)nview * HW;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, n = 0.f;
+    for (int sl = 0; sl < slices; ++sl) {
+        const size_t base = (size_t)sl * 4 * plane + (size_t)vl * HW + p;
+        s0 += part[base]; s1 += part[base + plane]; s2 += part[base + 2 * plane]; n += part[base + 3 * plane];
+    }
+    const bool k = d > 0.f && n >= num_consistent;
+    keep[e] = k ? 1 : 0;
+    const float inv = 1.0f / (n + 1.f);
+    fxyz[3 * e] = X0 + s0 * inv;
+    fxyz[3 * e + 1] = X1 + s1 * inv;
+    fxyz[3 * e + 2] = X2 + s2 * inv;
+    if (k && witness) {
+        int cnt = src_off[r + 1] - src_off[r];
+        cnt = cnt < 0 ? 0 : (cnt > max_src ? max_src : cnt);
+        for (int j = 0; j < cnt; ++j) {
+            const int w = witness[(size_t)j * HW + p];
+            if (w >= 0) used[w] = 1;        // always another view: idempotent stores, the race between writers is harmless
+        }
+    }
+}
+
+// Exclusive scan of one value per thread over a 256-thread block (Hillis-Steele in LDS); returns the thread's prefix.
+__device__ int fu_block_exclusive_scan(int v, int* sh, int& total) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int o = 1; o < FU_THREADS; o <<= 1) {
+        const int add = t >= o ? sh[t - o] : 0;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    total = sh[FU_THREADS - 1];
+    const int incl = sh[t];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(FU_THREADS) void fusion_count_kernel(const uint8_t* __restrict__ keep, size_t n, int* __restrict__ counts) {
+    __shared__ int sh[FU_THREADS];
+    const size_t e0 = (size_t)blockIdx.x * FU_CHUNK + 4 * threadIdx.x;
+    int c = 0;
+    for (int i = 0; i < 4; ++i) c += (e0 + i < n && keep[e0 + i]) ? 1 : 0;
+    int total;
+    fu_block_exclusive_scan(c, sh, total);
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// One workgroup: exclusive scan of the nb block counts into offs, the total into *count.
+__global__ __launch_bounds__(FU_THREADS) void fusion_scan_kernel(const int* __restrict__ counts, int nb, int* __restrict__ offs,
+                                                                  int* __restrict__ count) {
+    __shared__ int sh[FU_THREADS];
+    int carry = 0;
+    for (int b0 = 0; b0 < nb; b0 += FU_THREADS) {
+        const int b = b0 + threadIdx.x;
+        const int c = b < nb ? counts[b] : 0;
+        int total;
+        const int ex = fu_block_exclusive_scan(c, sh, total);
+        if (b < nb) offs[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+
+__global__ __launch_bounds__(FU_THREADS) void fusion_write_kernel(
+        const uint8_t* __restrict__ keep, const float* __restrict__ fxyz, size_t n, int HW, int W, const int* __restrict__ offs,
+        const uint8_t* __restrict__ images, int img_h, int img_w, int H, float* __restrict__ xyz, uint8_t* __restrict__ rgb,
+        int* __restrict__ view_index, int* __restrict__ pixel_index) {
+    __shared__ int sh[FU_THREADS];
+    const size_t e0 = (size_t)blockIdx.x * FU_CHUNK + 4 * threadIdx.x;
+    int c = 0;
+    for (int i = 0; i < 4; ++i) c += (e0 + i < n && keep[e0 + i]) ? 1 : 0;
+    int total;
+    int o = offs[blockIdx.x] + fu_block_exclusive_scan(c, sh, total);
+    for (int i = 0; i < 4; ++i) {
+        const size_t e = e0 + i;
+        if (e >= n || !keep[e]) continue;
+        xyz[3 * (size_t)o] = fxyz[3 * e];
+        xyz[3 * (size_t)o + 1] = fxyz[3 * e + 1];
+        xyz[3 * (size_t)o + 2] = fxyz[3 * e + 2];
+        const int v = (int)(e / HW), p = (int)(e % HW);
+        view_index[o] = v;
+        if (pixel_index) pixel_index[o] = p;
+        uint8_t c0 = 0, c1 = 0, c2 = 0;
+        if (images) {
+            const long long x = p % W, y = p / W;
+            const long long ix = (2 * x + 1) * img_w / (2 * (long long)W), iy = (2 * y + 1) * img_h / (2 * (long long)H);
+            const uint8_t* px = images + (((size_t)v * img_h + iy) * img_w + ix) * 3;
+            c0 = px[0]; c1 = px[1]; c2 = px[2];
+        }
+        rgb[3 * (size_t)o] = c0;
+        rgb[3 * (size_t)o + 1] = c1;
+        rgb[3 * (size_t)o + 2] = c2;
+        ++o;
+    }
+}
+
+size_t fu_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int fusion_slices(int HW, int max_src, int dedupe) {
+    if (!dedupe || max_src <= 1) return 1;
+    int s = mvs_cdiv(4096, mvs_cdiv(HW, 64));          // about 4096 waves per view launch
+    if (s > FU_MAX_SLICES) s = FU_MAX_SLICES;
+    if (s > max_src) s = max_src;
+    return s < 1 ? 1 : s;
+}
+
+struct FuLayout {
+    size_t df, used, part, witness, keep, fxyz, counts, offs, total;
+    int slices, nb;
+};
+
+FuLayout fusion_layout(int V, int H, int W, int max_src, int dedupe) {
+    FuLayout L{};
+    const size_t px = (size_t)V * H * W, HW = (size_t)H * W;
+    L.slices = fusion_slices((int)HW, max_src, dedupe);
+    L.nb = (int)((px + FU_CHUNK - 1) / FU_CHUNK);
+    const size_t nview = dedupe ? 1 : (size_t)V;
+    size_t o = 0;
+    L.df = o;      o += fu_align(px * sizeof(float));
+    L.used = o;    o += dedupe ? fu_align(px) : 0;
+    L.part = o;    o += fu_align((size_t)L.slices * 4 * nview * HW * sizeof(float));
+    L.witness = o; o += dedupe ? fu_align((size_t)max_src * HW * sizeof(int)) : 0;
+    L.keep = o;    o += fu_align(px);
+    L.fxyz = o;    o += fu_align(px * 3 * sizeof(float));
+    L.counts = o;  o += fu_align((size_t)L.nb * sizeof(int));
+    L.offs = o;    o += fu_align((size_t)L.nb * sizeof(int));
+    L.total = o;
+    return L;
+}
+
+bool fusion_shape_ok(int V, int H, int W, int max_src) {
+    if (V > 65535 || max_src > 65535) return false;
+    return (long long)V * H * W <= 0x7fffffffLL;
+}
+
+}  // namespace
+
+extern "C" size_t mvs_fusion_workspace_bytes(int V, int H, int W, int max_sources, int dedupe) {
+    if (V <= 0 || H <= 0 || W <= 0 || max_sources < 0 || !fusion_shape_ok(V, H, W, max_sources)) return 0;
+    return fusion_layout(V, H, W, max_sources, dedupe != 0).total;
+}
+
+extern "C" int mvs_fusion_f32(const float* depth, const float* prob, int V, int H, int W, const float* tables,
+                              const int* src_offsets, const int* src_index, int max_sources, float prob_threshold,
+                              float reproj_threshold, float depth_rel_threshold, float num_consistent, int dedupe,
+                              const uint8_t* images, int img_h, int img_w, float* xyz, uint8_t* rgb, int* view_index, int* pixel_index,
+                              int* count, void* workspace, size_t workspace_bytes, void* stream) {
+    MVS_CHECK_ARG(depth && prob && tables && src_offsets && xyz && rgb && view_index && count && workspace);
+    MVS_CHECK_ARG(V > 0 && H > 0 && W > 0 && max_sources >= 0 && (max_sources == 0 || src_index));
+    MVS_CHECK_ARG(!images || (img_h > 0 && img_w > 0));
+    MVS_CHECK_ARG(!__builtin_isnan(prob_threshold) && reproj_threshold > 0.f && depth_rel_threshold >= 0.f &&
+                  !__builtin_isnan(num_consistent));
+    if (!fusion_shape_ok(V, H, W, max_sources)) return MVS_E_SHAPE;
+    if (images && (long long)img_h * img_w * 3 * V > 0x7fffffffffffLL) return MVS_E_SHAPE;
+    const int dd = dedupe != 0;
+    const FuLayout L = fusion_layout(V, H, W, max_sources, dd);
+    if (workspace_bytes < L.total) return MVS_E_WORKSPACE;
+    hipStream_t st = mvs_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* df = reinterpret_cast<float*>(ws + L.df);
+    uint8_t* used = dd ? reinterpret_cast<uint8_t*>(ws + L.used) : nullptr;
+    float* part = reinterpret_cast<float*>(ws + L.part);
+    int* witness = dd ? reinterpret_cast<int*>(ws + L.witness) : nullptr;
+    uint8_t* keep = reinterpret_cast<uint8_t*>(ws + L.keep);
+    float* fxyz = reinterpret_cast<float*>(ws + L.fxyz);
+    int* counts = reinterpret_cast<int*>(ws + L.counts);
+    int* offs = reinterpret_cast<int*>(ws + L.offs);
+    const int HW = H * W;
+    const size_t px = (size_t)V * HW;
+    const float* M = tables;
+    const float* B = tables + (size_t)V * V * FU_TABLE;
+    const int chunk = max_sources > 0 ? mvs_cdiv(max_sources, L.slices) : 0;
+    const float reproj2 = reproj_threshold * reproj_threshold;
+    const unsigned gx = (unsigned)mvs_cdiv(HW, FU_THREADS);
+
+    hipLaunchKernelGGL(fusion_filter_kernel, dim3((unsigned)((px + FU_THREADS - 1) / FU_THREADS)), dim3(FU_THREADS), 0, st,
+                       depth, prob, px, prob_threshold, df);
+    if (dd) {
+        hipError_t e = hipMemsetAsync(used, 0, px, st);
+        if (e != hipSuccess) return (int)e;
+        for (int r = 0; r < V; ++r) {
+            hipLaunchKernelGGL(fusion_pairs_kernel, dim3(gx, 1, L.slices), dim3(FU_THREADS), 0, st, df, used, M, B, src_offsets,
+                               src_index, max_sources, V, H, W, r, chunk, reproj2, depth_rel_threshold, part, witness);
+            hipLaunchKernelGGL(fusion_finalize_kernel, dim3(gx, 1), dim3(FU_THREADS), 0, st, df, used, B, part, L.slices,
+                               src_offsets, witness, max_sources, H, W, r, num_consistent, keep, fxyz);
+        }
+    } else {
+        hipLaunchKernelGGL(fusion_pairs_kernel, dim3(gx, V, 1), dim3(FU_THREADS), 0, st, df, (const uint8_t*)nullptr, M, B,
+                           src_offsets, src_index, max_sources, V, H, W, 0, chunk, reproj2, depth_rel_threshold, part,
+                           (int*)nullptr);
+        hipLaunchKernelGGL(fusion_finalize_kernel, dim3(gx, V), dim3(FU_THREADS), 0, st, df, (uint8_t*)nullptr, B, part, 1,
+                           src_offsets, (const int*)nullptr, max_sources, H, W, 0, num_consistent, keep, fxyz);
+    }
+    hipLaunchKernelGGL(fusion_count_kernel, dim3(L.nb), dim3(FU_THREADS), 0, st, keep, px, counts);
+    hipLaunchKernelGGL(fusion_scan_kernel, dim3(1), dim3(FU_THREADS), 0, st, counts, L.nb, offs, count);
+    hipLaunchKernelGGL(fusion_write_kernel, dim3(L.nb), dim3(FU_THREADS), 0, st, keep, fxyz, px, HW, W, offs, images, img_h,
+                       img_w, H, xyz, rgb, view_index, pixel_index);
+    MVS_LAUNCH_RET();
+}

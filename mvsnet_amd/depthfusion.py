@@ -10,6 +10,11 @@
    (depthfusion.py:28-168);
 3. the external `fusibile` binary is run when it exists (depthfusion.py:192-213); it is not part of
    this package, so without it the converted folder is the result.
+With --fusion hip, steps 2 and 3 are replaced by this project's own geometric-consistency fusion on the GPU
+(mvsnet_amd.fusion: a HIP kernel, not bit-compatible with fusibile), which writes
+points_mvsnet/consistencyCheck-<YYYYmmdd-HHMMSS>/final3d_model.ply, the path the reference's scripts look for:
+    python -m mvsnet_amd.depthfusion --dense_folder <dir> --fusion hip [--reproj_threshold 1.0]
+        [--depth_rel_threshold 0.01] [--no_dedupe] [--fusion_sources {all,listed}]
 File formats are byte-compatible with the reference's writers (.dmb: int32 header 1,H,W,C +
 float32 data in the reference's element order).
 """
@@ -125,18 +130,64 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
     return subprocess.run(cmd, check=False).returncode
 
 
+def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent,
+               dedupe=True, fusion_sources="all"):
+    """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply."""
+    import time
+    from . import fusion
+    indices, depths, probs, cams, images = fusion.load_dense_folder(dense_folder)
+    sources = fusion.listed_sources(dense_folder, indices) if fusion_sources == "listed" else None
+    xyz, rgb, _ = fusion.fuse_depth_maps(depths, probs, cams, images, prob_threshold=prob_threshold,
+                                         reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold,
+                                         num_consistent=num_consistent, sources=sources, dedupe=dedupe)
+    out = os.path.join(point_folder, "consistencyCheck-" + time.strftime("%Y%m%d-%H%M%S"))
+    os.makedirs(out, exist_ok=True)
+    path = os.path.join(out, "final3d_model.ply")
+    fusion.write_ply(path, xyz, rgb)
+    print("fused %d views into %d points: %s" % (len(indices), len(xyz), path))
+    return path
+
+
+def _gpu_ready():
+    """None when the HIP library loads and a GPU is visible, else the reason."""
+    try:
+        import torch
+        from . import _lib
+        _lib.load()
+    except Exception as e:                     # library missing or not loadable
+        return str(e)
+    if not torch.cuda.is_available():
+        return "no GPU is visible to this process"
+    return None
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__)
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dense_folder", type=str, required=True)
     ap.add_argument("--fusibile_exe_path", type=str, default="")
     ap.add_argument("--prob_threshold", type=float, default=0.8)
-    ap.add_argument("--disp_threshold", type=float, default=0.25)
+    ap.add_argument("--disp_threshold", type=float, default=0.25, help="fusibile's disparity threshold (--fusion fusibile only)")
     ap.add_argument("--num_consistent", type=float, default=3)
+    ap.add_argument("--fusion", choices=("fusibile", "hip"), default="fusibile",
+                    help="fusibile: Gipuma hand-off + the external binary (default); hip: this project's GPU fusion")
+    ap.add_argument("--reproj_threshold", type=float, default=1.0, help="--fusion hip: reprojection error limit in pixels")
+    ap.add_argument("--depth_rel_threshold", type=float, default=0.01, help="--fusion hip: relative depth error limit")
+    ap.add_argument("--no_dedupe", action="store_true", help="--fusion hip: every view independent (witnesses not consumed)")
+    ap.add_argument("--fusion_sources", choices=("all", "listed"), default="all",
+                    help="--fusion hip: every other view, or the neighbours of pair.txt / covisibility.json in the dense folder")
     a = ap.parse_args(argv)
+    if a.fusion == "hip":
+        why = _gpu_ready()
+        if why is not None:
+            raise SystemExit("--fusion hip needs a GPU and the HIP library: %s" % why)
     point_folder = os.path.join(a.dense_folder, "points_mvsnet")
     os.makedirs(point_folder, exist_ok=True)
     print("filter depth map with probability map")
     probability_filter(a.dense_folder, a.prob_threshold)
+    if a.fusion == "hip":
+        print("Run depth map fusion & filter on the GPU")
+        return hip_fusion(a.dense_folder, point_folder, a.prob_threshold, a.reproj_threshold, a.depth_rel_threshold,
+                          a.num_consistent, dedupe=not a.no_dedupe, fusion_sources=a.fusion_sources)
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")
