@@ -14,7 +14,10 @@ from __future__ import annotations
 import argparse
 import logging
 import os
+import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
+from functools import partial
 
 import numpy as np
 
@@ -196,12 +199,274 @@ class SessionLoader:
 
 # Pinned host buffers are expensive to create (~1.5 ms each) and cheap to keep: the staging buffers of the uploads and the result
 # buffers of the downloads live for the process, not for one compute_depth_maps call (a session is one call).
-_PINNED_STAGING = {}
-_PINNED_RESULTS = {}
+_PINNED_STAGING = {}                                  # (shape, dtype) -> _Staging
+_PINNED_RESULTS = {}                                  # shape -> free pinned (depth, prob) buffer pairs
+
+
+class _Staging:                                       # two alternating pinned upload buffers and their last copies' events
+    def __init__(self):
+        self.bufs, self.events, self.next = [None, None], [None, None], 0
+
+
+def _upload(arrays, device):
+    """Same-shape host arrays -> one device tensor of their dtype, by an asynchronous copy on the current stream: from the
+    arrays' own pinned memory (host_pool.PinnedArray, no copy on this thread) or through the staging pair of their shape."""
+    import torch
+    arrays = list(arrays)
+    n, shp, dt = len(arrays), arrays[0].shape, arrays[0].dtype
+    pins = [getattr(a_, "pinned", None) for a_ in arrays]
+    if all(p_ is not None for p_ in pins):
+        dst = torch.empty((n,) + tuple(shp), dtype=pins[0].dtype, device=device)
+        for j, p_ in enumerate(pins):
+            dst[j].copy_(p_, non_blocking=True)
+        return dst
+    st = _PINNED_STAGING.setdefault((shp, dt), _Staging())
+    i, st.next = st.next, st.next ^ 1
+    if st.bufs[i] is None or st.bufs[i].shape[0] < n:
+        st.bufs[i] = torch.empty((max(n, 16),) + shp, dtype=torch.from_numpy(np.empty(0, dt)).dtype).pin_memory()
+    elif st.events[i] is not None:
+        st.events[i].synchronize()
+    view = st.bufs[i].numpy()
+    for j, a_ in enumerate(arrays):
+        view[j] = a_
+    t_ = st.bufs[i][:n].to(device, non_blocking=True)
+    st.events[i] = torch.cuda.current_stream(device).record_event()
+    return t_
+
+
+def _images_to_device(imgs, device, keep_uint8):
+    """Images -> device: uint8 ones stay uint8 with `keep_uint8` (the HIP towers standardise them in the library) and are
+    standardised here otherwise; float ones become float32."""
+    import torch
+    t_ = _upload(imgs, device)
+    if t_.dtype == torch.uint8:
+        return t_ if keep_uint8 else center_images_device(t_)
+    return t_.to(torch.float32)
+
+
+def _feature_keys(c, in_images, view_num):
+    """Feature-cache key of each view of a cluster: an image's features only depend on the image and the (rescale, crop) it got."""
+    ids = getattr(c, "indices", None) or list(getattr(c, "paths", [])[0::2])
+    return [(c.session_dir, ids[v], round(float(c.rescale), 9), in_images[v].shape) if v < len(ids) else ("view", id(c), v)
+            for v in range(view_num)]
+
+
+class _StageClock:
+    """Host seconds per stage (`tm`: this thread, the loader threads and the writer threads add to it) and GPU time between
+    (start, end) event pairs of tower passes, hot paths and hot-path end -> results in pinned memory.  All event work is
+    skipped without `timings`."""
+
+    def __init__(self, timings, pool, t_wall):
+        self.timings, self.on, self.pool, self.t_wall = timings, timings is not None, pool, t_wall
+        # submit_*: host_gpu_submit's parts: image upload + tower launches, feature stack, hot-path launches, result hand-over
+        self.tm = dict.fromkeys(("load", "wait_load", "host_gpu_submit", "write", "submit_towers", "submit_features",
+                                 "submit_depth", "submit_finish"), 0.0)
+        self.lock = threading.Lock()
+        self.spans = {"towers": [], "hot_path": [], "d2h": []}
+        self.cpu0 = None
+        if self.on:
+            try:
+                import psutil
+                self.cpu0 = (sum(psutil.Process().cpu_times()[:2]), pool.cpu_seconds() if pool is not None else 0.0)
+            except Exception:                         # noqa: BLE001
+                pass
+
+    def add(self, name, seconds):
+        with self.lock:
+            self.tm[name] += seconds
+
+    def timed(self, name, fn, *a):
+        t0 = time.perf_counter()
+        try:
+            return fn(*a)
+        finally:
+            self.add(name, time.perf_counter() - t0)
+
+    def mark(self):
+        import torch
+        return torch.cuda.current_stream().record_event(torch.cuda.Event(enable_timing=True)) if self.on else None
+
+    def span(self, kind, start, end):
+        if self.on:
+            self.spans[kind].append((start, end))
+
+    def report(self, done, n_loaders, n_writers):
+        if not self.on:
+            return
+        import torch
+        t = self.timings
+        torch.cuda.synchronize()
+        t.update(self.tm)
+        t["wall"] = time.perf_counter() - self.t_wall
+        t["depth_maps"] = done
+        t["loader_threads"], t["writer_threads"] = n_loaders, n_writers
+        t["host_workers"] = self.pool.workers if self.pool is not None else 0
+        if self.cpu0 is not None:
+            import psutil
+            t["host_cpu"] = (sum(psutil.Process().cpu_times()[:2]) - self.cpu0[0]) + \
+                            ((self.pool.cpu_seconds() or 0.0) - (self.cpu0[1] or 0.0) if self.pool is not None else 0.0)
+        for kind, spans in self.spans.items():
+            t[kind] = sum((a_.elapsed_time(b_) * 1e-3 for a_, b_ in spans), 0.0)
+
+
+class _ResultSink:
+    """`put`: a view's (depth, prob) -> a pinned host pair by an asynchronous copy on the compute stream, so this thread never
+    waits for the GPU (round 2 called .cpu() here) -> a writer thread, which waits for the copy's event and writes the files or
+    hands them to the worker processes.  At most 8 pairs are in flight: `put` blocks for a free one."""
+
+    WRITERS = 4
+
+    def __init__(self, config, output_dir, pool, clock):
+        self.config, self.output_dir, self.pool, self.clock = config, output_dir, pool, clock
+        self.slots = threading.BoundedSemaphore(8)
+        self.lock = threading.Lock()
+        self.writer = ThreadPoolExecutor(max_workers=self.WRITERS)
+        self.writes, self.pool_writes = [], []
+
+    def put(self, d, p, out_images, in_images, out_cams, full_cams, index):
+        """Returns the event of the copy to pinned memory."""
+        import torch
+        self.slots.acquire()
+        with self.lock:
+            free = _PINNED_RESULTS.setdefault(tuple(d.shape), [])
+            pair = free.pop() if free else None
+        if pair is None:
+            pair = (torch.empty(d.shape, dtype=torch.float32).pin_memory(), torch.empty(p.shape, dtype=torch.float32).pin_memory())
+        pair[0].copy_(d, non_blocking=True)
+        pair[1].copy_(p, non_blocking=True)
+        copied = torch.cuda.current_stream().record_event(torch.cuda.Event(enable_timing=self.clock.on))
+        self.writes.append(self.writer.submit(self._write, pair, copied, out_images, in_images, out_cams, full_cams, index))
+        return copied
+
+    def _write(self, pair, copied, out_images, in_images, out_cams, full_cams, index):
+        from . import predictlib as pl
+        cfg = self.config
+        try:                                          # the pair and its slot are released exactly once, on every path
+            copied.synchronize()
+            if cfg.refinement and cfg.upsample_before_refinement:         # full-size outputs (predictlib.py:107-115)
+                from .mvs_data_generation import center_image           # the reference writes the STANDARDISED input image here
+                img0 = center_image(in_images[0]) if in_images[0].dtype == np.uint8 else in_images[0]
+                args = (img0, full_cams[0], index, cfg.visualize, 1.0 / cfg.sample_scale)
+            else:
+                args = (out_images[0], out_cams[0], index, cfg.visualize, None)
+            if self.pool is None:
+                return self.clock.timed("write", pl.write_output_slice, self.output_dir, pair[0].numpy(), pair[1].numpy(), *args)
+            # private copies (the executor pickles them later, on its feeder thread), then the pinned pair is free again
+            dn, pn = np.array(pair[0].numpy()), np.array(pair[1].numpy())
+        finally:
+            with self.lock:
+                _PINNED_RESULTS[tuple(pair[0].shape)].append(pair)
+            self.slots.release()
+        f_ = self.pool.write_outputs(self.output_dir, dn, pn, np.asarray(args[0]), np.asarray(args[1]), *args[2:])
+        with self.lock:
+            self.pool_writes.append(f_)
+
+    def close(self):
+        """Waits for every write (raising what a writer raised) and returns the worker processes' write seconds."""
+        for w_ in self.writes:
+            w_.result()
+        seconds = sum((f_.result() for f_ in self.pool_writes), 0.0)
+        self.writer.shutdown()
+        return seconds
+
+
+class _ClusterFeed:
+    """Loads clusters `ahead` of the one in hand -- session format on the worker processes (SessionLoader) or on loader threads
+    as uint8, upstream pair.txt on loader threads standardised on the host -- and yields them in groups of up to `chunk`,
+    skipping and logging those that fail."""
+
+    def __init__(self, clusters, gen, pool, device, clock, n_loaders, ahead=16):
+        self.gen, self.clock = gen, clock
+        self.session_loader = SessionLoader(gen, pool, pin_device=device.index) if pool is not None else None
+        self.loader = ThreadPoolExecutor(max_workers=n_loaders)
+        self.it, self.pending = iter(clusters), []
+        for _ in range(ahead):
+            self._submit_next()
+
+    def _submit_next(self):
+        from .mvs_data_generation import Cluster
+        for c in self.it:
+            if type(c) is not Cluster:
+                load = self.loader.submit(self.clock.timed, "load", self.gen.prepare, c).result
+            elif self.session_loader is None:
+                load = self.loader.submit(self.clock.timed, "load", self.gen.prepare, c, False).result
+            else:
+                try:
+                    load = partial(self.session_loader.result, self.session_loader.submit(c))
+                except Exception as e:                # an unreadable header: skip-and-log like a failed load
+                    logger.warning("skipping cluster %s/%d: %s", c.session_dir, c.ref_index, e)
+                    continue
+            self.pending.append((c, load))
+            return
+
+    def groups(self, chunk):
+        while self.pending:
+            group, t0 = [], time.perf_counter()
+            while self.pending and len(group) < chunk:
+                c, load = self.pending.pop(0)
+                self._submit_next()
+                try:
+                    group.append((c, load()))
+                except Exception as e:                # skip-and-log per reference view
+                    logger.warning("skipping cluster %s/%d: %s", c.session_dir, c.ref_index, e)
+            self.clock.add("wait_load", time.perf_counter() - t0)
+            if group:
+                yield group
+
+    def close(self):
+        """Returns the worker processes' load seconds (the loader threads' are in the clock already)."""
+        self.loader.shutdown()
+        return self.session_loader.load_seconds if self.session_loader is not None else 0.0
+
+
+def _starts_new_sweep(batch, shape, depth_num):
+    """A recurrent sweep takes views of one feature shape and depth count: a view unlike the pending ones sends them off first."""
+    return bool(batch) and (batch[0][0].shape != shape or batch[0][2] != depth_num)
+
+
+class _GruBatcher:
+    """Up to `views` reference views of the GRU regulariser in one sweep (mvs_gru_wta_batch_f32), a DepthPlan per shape."""
+
+    def __init__(self, config, weights, device, views, sink, clock):
+        self.config, self.weights, self.device, self.views, self.sink, self.clock = config, weights, device, views, sink, clock
+        self.batch, self.plans = [], {}
+
+    def add(self, features, cams, depth_num, depth_start, depth_end, rest):
+        if _starts_new_sweep(self.batch, features.shape, depth_num):
+            self.flush()
+        self.batch.append((features, cams, depth_num, depth_start, depth_end, rest))
+        if len(self.batch) >= self.views:
+            self.flush()
+
+    def flush(self):
+        if not self.batch:
+            return
+        from .model import DepthPlan, wta_depth_values
+        cfg = self.config
+        _, Hf, Wf, Cf = self.batch[0][0].shape
+        key = (self.batch[0][2], Hf, Wf, Cf)
+        plan = self.plans.get(key)
+        if plan is None:
+            plan = self.plans[key] = DepthPlan(cfg.view_num, key[0], Hf, Wf, Cf, self.weights, "GRU", self.device, views=self.views)
+        dvs = []
+        for v, (_f, cams, D, start, end, _rest) in enumerate(self.batch):
+            interval = float((np.float32(end) - np.float32(start)) / (np.float32(D) - np.float32(1)))      # model.py:606-607
+            plan.set_cameras(cams, start, interval, end, cfg.inverse_depth, view=v)
+            dvs.append(wta_depth_values(D, start, end, cfg.inverse_depth))
+        m0 = self.clock.mark()
+        dd, pp_ = plan.run_gru_batch([b_[0] for b_ in self.batch], dvs)
+        m1 = self.clock.mark()
+        self.clock.span("hot_path", m0, m1)
+        for v, b_ in enumerate(self.batch):
+            # copied out in stream order, before the next sweep overwrites the plan's buffers
+            copied = self.sink.put(dd[v], pp_[v], *b_[5])
+            if v == 0:
+                self.clock.span("d2h", m1, copied)
+        self.batch = []
 
 
 def compute_depth_maps(input_dir, config=None, weights=None, device=None, timings=None, gru_views=4,
-                       feature_cache_limit=256, host_workers=None, tower_stream=True, **kwargs):
+                       feature_cache_limit=256, host_workers=None, **kwargs):
     """mvsnet/inference.py:83-119.  Returns the number of depth maps this rank wrote.
 
     `timings` (a dict) receives the stage breakdown of the run in seconds: wall, load (decode + resize + crop + centre on the
@@ -210,14 +475,10 @@ def compute_depth_maps(input_dir, config=None, weights=None, device=None, timing
     writers, summed over threads).  `gru_views`: reference views per recurrent sweep (mvs_gru_wta_batch_f32) with the GRU
     regulariser.  `host_workers`: worker PROCESSES for image decoding / rescaling and output encoding (host_pool; None = by
     core count, 0 = round 3's loader / writer threads inside this process); `timings` then also receives host_cpu = CPU
-    seconds of this process and its workers.  `tower_stream`: the image uploads and the UNetDS2GN towers of a group of reference
-    views go to a HIP stream of their own and the hot path waits for their event -- this thread runs several views ahead of the
-    GPU, so the (launch-bound) towers of group g + 1 execute beside the hot path of group g instead of in line with it."""
-    import threading
+    seconds of this process and its workers."""
     import torch
-    from . import predictlib as pl
-    from . import shard as sh
-    from .mvs_data_generation import make_generator
+    from . import host_pool, predictlib as pl, shard as sh
+    from .mvs_data_generation import Cluster, make_generator
 
     config = config or pl.InferenceConfig()
     for k, v in kwargs.items():                       # predictlib.init_inference: kwargs -> flags
@@ -242,335 +503,72 @@ def compute_depth_maps(input_dir, config=None, weights=None, device=None, timing
     if weights is None:
         weights = build_weights(config, device)
     t_wall = time.perf_counter()
-    tm = {"load": 0.0, "wait_load": 0.0, "host_gpu_submit": 0.0, "write": 0.0,
-          # parts of host_gpu_submit (this thread): image upload + tower launches, feature stack, hot-path launches, result hand-over
-          "submit_towers": 0.0, "submit_features": 0.0, "submit_depth": 0.0, "submit_finish": 0.0}
-    tm_lock = threading.Lock()
-
-    def timed(name, fn, *a):
-        t0 = time.perf_counter()
-        try:
-            return fn(*a)
-        finally:
-            with tm_lock:
-                tm[name] += time.perf_counter() - t0
-
-    # Per-image feature cache: the reference re-runs the UNetDS2GN tower on
-    # every source image of every cluster (model.py:392-406); an image's features only depend on
-    # the image and on the (rescale, crop) it received, so they are computed once per session and
-    # re-used by all the reference views that list the image as a source.
-    feature_cache = FeatureCache(feature_cache_limit)
-    done = 0
-    # Host pipeline: like the reference, whose generator runs in a tf.data thread with a prefetch buffer
-    # (predictlib.py:48-51), image loading / resizing of the next clusters and the file writes of the previous ones run
-    # on worker threads (numpy / PIL / file IO release the GIL); this thread only drives the GPU and never waits for it:
-    # results go device -> PINNED host buffers with an asynchronous copy, and the writer thread that owns a buffer waits for
-    # the copy's event (round 2 called .cpu() here, which held this thread -- and with it the next reference view's launches
-    # -- until the GPU had finished the current one).
-    from concurrent.futures import ThreadPoolExecutor
-    from . import host_pool
-    from .mvs_data_generation import Cluster
-    n_loaders = max(2, min(8, (os.cpu_count() or 4) // 2))
-    n_writers = 4
-    # Round 4: the per-image work of the loaders and the whole of the writers run in worker PROCESSES (host_pool): with them on
-    # threads of this process the thread that feeds the GPU spent more time waiting for the GIL than working.  The loader /
-    # writer threads below remain as the thin ends of that pipe (they wait for futures and copy events), and as the whole
-    # pipe for upstream-format projects and for host_workers = 0.
+    # Like the reference's tf.data prefetch (predictlib.py:48-51), loads and writes run off this thread, which only drives the
+    # GPU; since round 4 their per-image work runs in worker PROCESSES (on threads, this thread mostly waited for the GIL).
+    # Loader / writer threads are the thin ends of that pipe, and the whole pipe for pair.txt projects and host_workers = 0.
     pool = host_pool.get_pool(host_workers) if any(type(c_) is Cluster for c_ in mine) else None
-    session_loader = SessionLoader(gen, pool, pin_device=device.index) if pool is not None else None
-    cpu0 = None
-    if timings is not None:
-        try:
-            import psutil
-            cpu0 = (sum(psutil.Process().cpu_times()[:2]), pool.cpu_seconds() if pool is not None else 0.0)
-        except Exception:                             # noqa: BLE001
-            cpu0 = None
-    loader, writer = ThreadPoolExecutor(max_workers=n_loaders), ThreadPoolExecutor(max_workers=n_writers)
-    pending, writes, pool_writes = [], [], []
-    ahead = 16
-    slots = threading.BoundedSemaphore(8)             # pinned result buffers in flight
-    ev_marks = []                                     # per reference view: events at the stage boundaries
-
-    device_center = lambda c_: type(c_) is Cluster        # session format: uint8 up, standardised on the device
-
-    class _Handle:                                        # a cluster whose images are on their way through the worker processes
-        def __init__(self, h):
-            self.h = h
-
-        def result(self):
-            return session_loader.result(self.h)
-
-    def submit_next(it):
-        for c_ in it:
-            if device_center(c_) and session_loader is not None:
-                try:
-                    pending.append((c_, _Handle(session_loader.submit(c_))))
-                except Exception as e:                    # an unreadable header: skip-and-log like a failed load
-                    logger.warning("skipping cluster %s/%d: %s", c_.session_dir, c_.ref_index, e)
-                    continue
-            elif device_center(c_):
-                pending.append((c_, loader.submit(timed, "load", gen.prepare, c_, False)))
-            else:
-                pending.append((c_, loader.submit(timed, "load", gen.prepare, c_)))
-            return
-
-    def keys_of(c, in_images):
-        ids = getattr(c, "indices", None) or [p_ for p_ in getattr(c, "paths", [])[0::2]]
-        return [(c.session_dir, ids[v], round(float(c.rescale), 9), in_images[v].shape) if v < len(ids) else ("view", id(c), v)
-                for v in range(config.view_num)]
-
-    staging = _PINNED_STAGING                         # (shape, dtype) -> [pinned buffers, their last copy's event, next index]
-
-    def to_device(imgs):
-        """list / array of images -> device float32, standardised there when they come as uint8.  The upload goes through two
-        alternating pinned staging buffers (asynchronous copy; a buffer is re-filled only after its previous copy's event)."""
-        imgs = list(imgs)
-        n, shp, dt = len(imgs), imgs[0].shape, imgs[0].dtype
-        pins = [getattr(im, "pinned", None) for im in imgs]
-        if all(p_ is not None for p_ in pins):        # already in pinned memory (host_pool.PinnedArray): no copy on this thread
-            dst = torch.empty((n,) + tuple(shp), dtype=pins[0].dtype, device=device)
-            for j, p_ in enumerate(pins):
-                dst[j].copy_(p_, non_blocking=True)
-            return dst
-        st_ = staging.setdefault((shp, dt), [[None, None], [None, None], 0])
-        i_ = st_[2]; st_[2] ^= 1
-        cap = 0 if st_[0][i_] is None else st_[0][i_].shape[0]
-        if cap < n:
-            st_[0][i_] = torch.empty((max(n, 16),) + shp, dtype=torch.from_numpy(np.empty(0, dt)).dtype).pin_memory()
-        elif st_[1][i_] is not None:
-            st_[1][i_].synchronize()
-        buf = st_[0][i_]
-        view = buf.numpy()
-        for j, im in enumerate(imgs):
-            view[j] = im
-        t_ = buf[:n].to(device, non_blocking=True)
-        ev = torch.cuda.Event(); ev.record(); st_[1][i_] = ev
-        return t_
-
-    towers_take_u8 = bool(getattr(weights.unet, "takes_uint8", False))    # HipUNetDS2GN standardises uint8 input in the library
-
-    def images_to_device(imgs):
-        t_ = to_device(imgs)
-        if t_.dtype == torch.uint8:
-            return t_ if towers_take_u8 else center_images_device(t_)
-        return t_.to(torch.float32)
-
-    def prefetch_features(group):
-        """The images of these reference views that the cache misses go through the towers as ONE batch (a tower pass is ~31
-        launches on a ~25 us floor each: one image costs nearly as much as sixteen)."""
-        feature_cache.fill(((k_, res_[1][v]) for c_, res_ in group for v, k_ in enumerate(keys_of(c_, res_[1]))),
-                           lambda imgs: weights.unet(images_to_device(imgs)))
-
-    # the towers' stream (see `tower_stream`); feature maps are allocated there and read on the compute stream: record_stream keeps
-    # the caching allocator from handing a freed map's memory out again while the compute stream may still be reading it
-    t_stream = torch.cuda.Stream(device) if (tower_stream and weights.unet is not None) else None
-
-    def features_of(c, in_images):
-        """(N,H/4,W/4,C) of one reference view from the per-image cache (pinned for the group by prefetch_features)."""
-        maps = feature_cache.get(keys_of(c, in_images))
-        if t_stream is not None:
-            cur = torch.cuda.current_stream(device)
-            for m_ in maps:
-                m_.record_stream(cur)
-        return torch.stack(maps).contiguous()
-
-    pinned = _PINNED_RESULTS                          # shape -> free pinned (depth, prob) buffer pairs, re-used across reference views
-
-    def finish(d, p, out_images, in_images, out_cams, full_cams, index, marks):
-        """device results -> pinned host buffers (asynchronous copy on the compute stream, no host wait) -> writer thread"""
-        slots.acquire()
-        with tm_lock:
-            free = pinned.setdefault(tuple(d.shape), [])
-            pair = free.pop() if free else None
-        if pair is None:
-            pair = (torch.empty(d.shape, dtype=torch.float32).pin_memory(), torch.empty(p.shape, dtype=torch.float32).pin_memory())
-        dh, ph = pair
-        dh.copy_(d, non_blocking=True); ph.copy_(p, non_blocking=True)
-        copied = torch.cuda.Event(enable_timing=timings is not None)
-        copied.record()
-        if marks is not None:
-            marks.append(copied)
-
-        def write():
-            released = False
-
-            def release():
-                nonlocal released
-                if not released:
-                    released = True
-                    with tm_lock:
-                        pinned[tuple(dh.shape)].append(pair)
-                    slots.release()
-            try:
-                copied.synchronize()
-                full = bool(config.refinement and config.upsample_before_refinement)      # full-size outputs (predictlib.py:107-115)
-                if full:
-                    from .mvs_data_generation import center_image       # the reference writes the STANDARDISED input image here
-                    img0 = center_image(in_images[0]) if in_images[0].dtype == np.uint8 else in_images[0]
-                    args = (img0, full_cams[0], index, config.visualize, 1.0 / config.sample_scale)
-                else:
-                    args = (out_images[0], out_cams[0], index, config.visualize, None)
-                if pool is None:
-                    return timed("write", pl.write_output_slice, output_dir, dh.numpy(), ph.numpy(), *args)
-                # private copies (the executor pickles them later, on its feeder thread), then the pinned pair is free again
-                dn, pn = np.array(dh.numpy()), np.array(ph.numpy())
-                release()
-                f_ = pool.write_outputs(output_dir, dn, pn, np.asarray(args[0]), np.asarray(args[1]), *args[2:])
-                with tm_lock:
-                    pool_writes.append(f_)
-            finally:
-                release()
-        writes.append(writer.submit(write))
-
-    def mark():
-        if timings is None:
-            return None
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
-
-    gru_batch = []                                    # GRU: reference views waiting to share one sweep
-    tower_marks = []                                  # (start, end) events of tower passes not yet attributed to a flushed sweep
-
-    def flush_gru():
-        if not gru_batch:
-            return
-        from .model import DepthPlan, wta_depth_values
-        t0 = time.perf_counter()
-        feats0 = gru_batch[0][0]
-        _, Hf, Wf, Cf = feats0.shape
-        D = gru_batch[0][2]
-        key = ("gru", config.view_num, D, Hf, Wf, Cf, id(weights), max(1, gru_views))
-        plan = plan_cache.get(key)
-        if plan is None:
-            plan = plan_cache[key] = DepthPlan(config.view_num, D, Hf, Wf, Cf, weights, "GRU", device, views=max(1, gru_views))
-        dvs = []
-        for v, (f_, cams_, D_, start_, end_, _rest) in enumerate(gru_batch):
-            interval_ = float((np.float32(end_) - np.float32(start_)) / (np.float32(D_) - np.float32(1)))      # model.py:606-607
-            plan.set_cameras(cams_, start_, interval_, end_, config.inverse_depth, view=v)
-            dvs.append(wta_depth_values(D_, start_, end_, config.inverse_depth))
-        m0 = mark()
-        dd, pp_ = plan.run_gru_batch([g_[0] for g_ in gru_batch], dvs)
-        m1 = mark()
-        for v, g_ in enumerate(gru_batch):
-            # the tower passes (and uploads) of the groups that fed this sweep: their event pairs ride on its first view
-            marks = [None, None, m0, m1] if (timings is not None and v == 0) else None
-            if marks is not None and tower_marks:
-                marks[0], marks[1] = tower_marks.pop(0)
-                ev_marks.extend([[a_, b_, m0, m0] for a_, b_ in tower_marks])      # further groups: towers only (zero-length hot path)
-                tower_marks.clear()
-            finish(dd[v], pp_[v], *g_[5], marks)        # copied out in stream order, before the next sweep overwrites the plan's buffers
-            if marks is not None:
-                ev_marks.append(marks)
-        gru_batch.clear()
-
-    plan_cache = {}
-    it = iter(mine)
-    for _ in range(ahead):
-        submit_next(it)
-    warm_device_one_offs(device, centre=not towers_take_u8)
-    chunk = 8                                         # reference views per tower pass (their new images form one batch)
-    # (round 6 measured a ramp of 2, 4, 8 views for the first groups: no gain -- the worker processes decode a group's images in
-    #  parallel, so the first group of eight is ready as soon as a group of two would be: 555-570 against 567-583 depth maps/s)
-    while pending:
-        group = []
-        t0 = time.perf_counter()
-        while pending and len(group) < chunk:
-            c, fut = pending.pop(0)
-            submit_next(it)
-            try:
-                group.append((c, fut.result()))
-            except Exception as e:                    # skip-and-log per reference view (SURVEY 5)
-                logger.warning("skipping cluster %s/%d: %s", c.session_dir, c.ref_index, e)
+    clock = _StageClock(timings, pool, t_wall)
+    sink = _ResultSink(config, output_dir, pool, clock)
+    n_loaders = max(2, min(8, (os.cpu_count() or 4) // 2))
+    feed = _ClusterFeed(mine, gen, pool, device, clock, n_loaders)
+    gru = (_GruBatcher(config, weights, device, gru_views, sink, clock)
+           if config.regularization == "GRU" and gru_views > 1 and not config.refinement else None)
+    # the reference re-runs the towers on every source image of every cluster (model.py:392-406): SURVEY 8a R11 / 8f f2
+    feature_cache = FeatureCache(feature_cache_limit)
+    takes_u8 = bool(getattr(weights.unet, "takes_uint8", False))    # HipUNetDS2GN standardises uint8 input in the library
+    warm_device_one_offs(device, centre=not takes_u8)
+    # Uploads + towers of a group run on a stream of their own, beside the hot path of the previous group.  Their feature maps
+    # are read on the compute stream: record_stream keeps the allocator from reusing a freed map that is still being read.
+    t_stream, compute = torch.cuda.Stream(device), torch.cuda.current_stream(device)
+    done = 0
+    # 8 reference views per tower pass, their new images in one batch (~31 launches on a ~25 us floor: one image costs nearly
+    # as much as sixteen).  Round 6: a ramp of 2, 4, 8 views for the first groups gained nothing (555-570 vs 567-583 maps/s).
+    for group in feed.groups(chunk=8):
         t1 = time.perf_counter()
-        tm["wait_load"] += t1 - t0
-        if not group:
-            continue
-        if t_stream is not None:
-            with torch.cuda.stream(t_stream):
-                m_start = mark()
-                prefetch_features(group)
-                m_towers = mark()
-                towers_done = t_stream.record_event()
-            torch.cuda.current_stream(device).wait_event(towers_done)
-        else:
-            m_start = mark()
-            prefetch_features(group)
-            m_towers = mark()
-        tm["submit_towers"] += time.perf_counter() - t1
+        with torch.cuda.stream(t_stream):
+            m_start = clock.mark()
+            feature_cache.fill(((k_, res_[1][v]) for c_, res_ in group
+                                for v, k_ in enumerate(_feature_keys(c_, res_[1], config.view_num))),
+                               lambda imgs: weights.unet(_images_to_device(imgs, device, keep_uint8=takes_u8)))
+            clock.span("towers", m_start, clock.mark())
+            towers_done = t_stream.record_event()
+        compute.wait_event(towers_done)
+        clock.add("submit_towers", time.perf_counter() - t1)
         # the group's cameras in ONE upload through pinned staging (a pageable .to(device) per reference view is a blocking
         # copy queued behind the previous view's kernels: it cost this thread ~0.6 ms per view)
-        cams_group = to_device([np.asarray(res_[2], dtype=np.float32) for _c, res_ in group])
-        first = True
-        for gi, (c, (out_images, in_images, out_cams, full_cams, index)) in enumerate(group):
-            start = time.time()
-            t_a = time.perf_counter()
-            features = features_of(c, in_images)
-            tm["submit_features"] += time.perf_counter() - t_a
-            cams = cams_group[gi]
-            depth_start = float(out_cams[0, 1, 3, 0])     # predictlib.set_shapes :190-197
-            depth_interval = float(out_cams[0, 1, 3, 1])
-            depth_num = int(out_cams[0, 1, 3, 2])
-            depth_end = float(out_cams[0, 1, 3, 3])
-            rest = (out_images, in_images, out_cams, full_cams, index)
-            batched_gru = (config.regularization == "GRU" and gru_views > 1 and not config.refinement and
-                           (not gru_batch or (gru_batch[0][0].shape == features.shape and gru_batch[0][2] == depth_num)))
-            if config.regularization == "GRU" and gru_views > 1 and not config.refinement and not batched_gru:
-                flush_gru()                               # a view of another size starts a new batch
-                batched_gru = True
-            if batched_gru:
-                if first and timings is not None:
-                    tower_marks.append((m_start, m_towers))
-                gru_batch.append((features, cams, depth_num, depth_start, depth_end, rest))
-                if len(gru_batch) >= gru_views:
-                    flush_gru()
+        cams_group = _upload([np.asarray(res_[2], dtype=np.float32) for _c, res_ in group], device)
+        for gi, (c, rest) in enumerate(group):
+            out_images, in_images, out_cams, full_cams, index = rest
+            start, t_a = time.time(), time.perf_counter()
+            maps = feature_cache.get(_feature_keys(c, in_images, config.view_num))
+            for m_ in maps:
+                m_.record_stream(compute)
+            features = torch.stack(maps).contiguous()
+            clock.add("submit_features", time.perf_counter() - t_a)
+            depth_start, depth_interval = float(out_cams[0, 1, 3, 0]), float(out_cams[0, 1, 3, 1])  # predictlib.set_shapes :190-197
+            depth_num, depth_end = int(out_cams[0, 1, 3, 2]), float(out_cams[0, 1, 3, 3])
+            if gru is not None:
+                gru.add(features, cams_group[gi], depth_num, depth_start, depth_end, rest)
             else:
-                ref_image = images_to_device(in_images[0:1]) if config.refinement else None
-                m_a = mark()
-                t_b = time.perf_counter()
-                d, p, _ = pl.get_depth_and_prob_map(None, cams[None], depth_start, depth_interval, config, weights,
+                # ADVICE "high": the guide image should be standardised (keep_uint8=False); fixed in a follow-up
+                ref_image = _images_to_device(in_images[0:1], device, keep_uint8=takes_u8) if config.refinement else None
+                m_a, t_b = clock.mark(), time.perf_counter()
+                d, p, _ = pl.get_depth_and_prob_map(None, cams_group[gi][None], depth_start, depth_interval, config, weights,
                                                     depth_num=depth_num, depth_end=depth_end, features=features,
                                                     ref_image=ref_image)
-                m_depth = mark()
-                t_c = time.perf_counter()
-                tm["submit_depth"] += t_c - t_b
-                marks = [m_start if first else None, m_towers if first else None, m_a, m_depth] if timings is not None else None
-                finish(d, p, *rest, marks)
-                tm["submit_finish"] += time.perf_counter() - t_c
-                if marks is not None:
-                    ev_marks.append(marks)
-            first = False
+                m_depth, t_c = clock.mark(), time.perf_counter()
+                clock.add("submit_depth", t_c - t_b)
+                clock.span("hot_path", m_a, m_depth)
+                clock.span("d2h", m_depth, sink.put(d, p, *rest))
+                clock.add("submit_finish", time.perf_counter() - t_c)
             done += 1
             logger.info("Depth inference %d/%d finished. (%.3f sec/step)", done, len(mine), time.time() - start)
-        with tm_lock:
-            tm["host_gpu_submit"] += time.perf_counter() - t1
-    flush_gru()
-    for w_ in writes:
-        w_.result()                                   # surfaces write errors; all files are on disk on return
-    for f_ in pool_writes:
-        tm["write"] += f_.result()                    # worker seconds; raises what the worker raised
-    if session_loader is not None:
-        tm["load"] += session_loader.load_seconds
-    loader.shutdown(); writer.shutdown()
-    if timings is not None:
-        torch.cuda.synchronize()
-        timings.update(tm)
-        timings["wall"] = time.perf_counter() - t_wall
-        timings["depth_maps"] = done
-        timings["loader_threads"], timings["writer_threads"] = n_loaders, n_writers
-        timings["host_workers"] = pool.workers if pool is not None else 0
-        if cpu0 is not None:
-            import psutil
-            timings["host_cpu"] = (sum(psutil.Process().cpu_times()[:2]) - cpu0[0]) + \
-                                  ((pool.cpu_seconds() or 0.0) - (cpu0[1] or 0.0) if pool is not None else 0.0)
-        tw = th = td = 0.0
-        for m in ev_marks:
-            if m[0] is not None and m[1] is not None:
-                tw += m[0].elapsed_time(m[1]) * 1e-3
-            th += m[2].elapsed_time(m[3]) * 1e-3
-            if len(m) > 4:
-                td += m[3].elapsed_time(m[4]) * 1e-3
-        timings["towers"], timings["hot_path"], timings["d2h"] = tw, th, td
+        clock.add("host_gpu_submit", time.perf_counter() - t1)
+    if gru is not None:
+        gru.flush()
+    clock.add("write", sink.close())                  # surfaces write errors; all files are on disk on return
+    clock.add("load", feed.close())
+    clock.report(done, n_loaders, _ResultSink.WRITERS)
     return done
 
 

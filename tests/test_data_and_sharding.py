@@ -304,6 +304,16 @@ def test_feature_cache_never_evicts_a_key_of_the_group_in_hand():
         c.get([6])                                                                     # not part of the group in hand
 
 
+def test_a_recurrent_sweep_takes_views_of_one_feature_shape_and_depth_count():
+    """The GRU batcher sends the pending views off before a view of another feature shape or depth count joins them."""
+    from mvsnet_amd.inference import _starts_new_sweep
+    pending = [(np.zeros((5, 128, 160, 32), np.float32), "cams", 192)]
+    assert not _starts_new_sweep([], (5, 96, 128, 32), 96)
+    assert not _starts_new_sweep(pending, (5, 128, 160, 32), 192)
+    assert _starts_new_sweep(pending, (5, 96, 128, 32), 192)
+    assert _starts_new_sweep(pending, (5, 128, 160, 32), 96)
+
+
 def test_host_worker_processes_equal_the_in_process_loader_and_writer(tmp_path):
     """mvsnet_amd/host_pool.py (round 4): the per-image part of the loader (decode -> scale-to-cover -> centre-crop -> output
     scale) and write_output_slice run in spawned worker PROCESSES; a cluster assembled by inference.SessionLoader equals
