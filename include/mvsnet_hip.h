@@ -594,6 +594,46 @@ int mvs_fusion_f32(const float* depth, const float* prob, int V, int H, int W, c
                    float* xyz, uint8_t* rgb, int* view_index, int* pixel_index, int* count, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* Point-cloud evaluation (csrc/pointcloud.hip; semantics in mvsnet_amd/evaluate.py).  Points are (n,3) float32, n >= 1.
+ *
+ * Nearest neighbour of every query point in the target cloud, capped at max_dist:
+ *   grid          the target's uniform grid: origin (ox, oy, oz), cubic cells of side `cell`, gx * gy * gz cells
+ *                 (MVS_E_SHAPE beyond 2^24); points outside it are clamped into its border cells, any grid gives exact results
+ *   dist, index   (n_query) float32 / int32, in query input order: d = min over the target of |q - t| (d^2 in float32 from
+ *                 float32 differences) and the target index of the minimiser when d^2 <= max_dist^2, else +inf and -1; exact
+ *                 ties of d^2 go to the smallest target index
+ *   workspace     mvs_nn_workspace_bytes(n_query, n_target, gx, gy, gz) bytes (0 for invalid sizes)
+ * Deterministic: the only atomics are integer ranks inside a cell, and the answer does not depend on them. */
+size_t mvs_nn_workspace_bytes(int n_query, int n_target, int gx, int gy, int gz);
+int mvs_nn_f32(const float* query, int n_query, const float* target, int n_target, float ox, float oy, float oz, float cell,
+               int gx, int gy, int gz, float max_dist, float* dist, int* index, void* workspace, size_t workspace_bytes,
+               void* stream);
+/* The query step of mvs_nn_f32 alone, over the grid and the sorted copies that the last mvs_nn_f32 call with the same sizes,
+ * grid and workspace left there (for another max_dist, or to time the query apart from the grid builds); visited (n_query)
+ * int32 or NULL receives the number of candidate target points each query compared (a measurement). */
+int mvs_nn_query_f32(int n_query, int n_target, float ox, float oy, float oz, float cell, int gx, int gy, int gz,
+                     float max_dist, float* dist, int* index, int* visited, const void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* Statistics of a distance array (inf = beyond):
+ *   thresholds    [host] n_thresholds floats, each 0 < tau <= max_dist (MVS_E_BADARG otherwise); at most 16 (MVS_E_SHAPE)
+ *   out           2 + n_thresholds doubles: sum of d over d < max_dist, count of d < max_dist, count of d < tau_t per threshold
+ *   workspace     mvs_dist_stats_workspace_bytes(n, n_thresholds) bytes
+ * float64 partial sums per block reduced in block order, integer counts: the same input gives the same bytes. */
+size_t mvs_dist_stats_workspace_bytes(int n, int n_thresholds);
+int mvs_dist_stats_f32(const float* dist, int n, float max_dist, const float* thresholds, int n_thresholds, double* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* Voxel downsampling, first point in input order per occupied voxel, in two calls around a stable sort of the keys:
+ *   mvs_voxel_keys_f32    keys (n) int64 = kx | ky << 21 | kz << 42, k = floor((x - min) / cell) per axis in float64; the
+ *                         caller guarantees k < 2^21 (larger values are clamped)
+ *   mvs_voxel_select_f32  sorted_keys (n) int64 and order (n) int64, the keys after a STABLE ascending sort and the input
+ *                         index of each; out (n,3) float32 receives the kept points in input order, count (one int32) their
+ *                         number; workspace mvs_voxel_select_workspace_bytes(n) bytes */
+int mvs_voxel_keys_f32(const float* xyz, int n, double min_x, double min_y, double min_z, double cell, long long* keys,
+                       void* stream);
+size_t mvs_voxel_select_workspace_bytes(int n);
+int mvs_voxel_select_f32(const float* xyz, int n, const long long* sorted_keys, const long long* order, float* out, int* count,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,14 @@ SIGNATURES = {
     "mvs_regnet_filler_shares": (_i, [C.POINTER(C.c_int)]),
     "mvs_fusion_workspace_bytes": (_sz, [_i] * 5),
     "mvs_fusion_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mvs_nn_workspace_bytes": (_sz, [_i] * 5),
+    "mvs_nn_f32": (_i, [_p, _i, _p, _i, _f, _f, _f, _f, _i, _i, _i, _f, _p, _p, _p, _sz, _p]),
+    "mvs_nn_query_f32": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "mvs_dist_stats_workspace_bytes": (_sz, [_i, _i]),
+    "mvs_dist_stats_f32": (_i, [_p, _i, _f, C.POINTER(C.c_float), _i, _p, _p, _sz, _p]),
+    "mvs_voxel_keys_f32": (_i, [_p, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
+    "mvs_voxel_select_workspace_bytes": (_sz, [_i]),
+    "mvs_voxel_select_f32": (_i, [_p, _i, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}

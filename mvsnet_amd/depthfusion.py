@@ -15,6 +15,8 @@ With --fusion hip, steps 2 and 3 are replaced by this project's own geometric-co
 points_mvsnet/consistencyCheck-<YYYYmmdd-HHMMSS>/final3d_model.ply, the path the reference's scripts look for:
     python -m mvsnet_amd.depthfusion --dense_folder <dir> --fusion hip [--reproj_threshold 1.0]
         [--depth_rel_threshold 0.01] [--no_dedupe] [--fusion_sources {all,listed}]
+        [--eval_gt G.ply [--eval_max_dist 20] [--eval_thresholds 0.5,1,2]]
+and, with --eval_gt, evaluates that cloud against a ground-truth PLY on the GPU (mvsnet_amd.evaluate) into metrics.json beside it.
 File formats are byte-compatible with the reference's writers (.dmb: int32 header 1,H,W,C +
 float32 data in the reference's element order).
 """
@@ -131,20 +133,32 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
 
 
 def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent,
-               dedupe=True, fusion_sources="all"):
-    """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply."""
+               dedupe=True, fusion_sources="all", eval_gt=None, eval_max_dist=20.0, eval_thresholds=()):
+    """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply.
+    With eval_gt (a PLY), the fused cloud is evaluated against it on the device (mvsnet_amd.evaluate) and the metrics are
+    written to metrics.json next to the PLY."""
+    import json
     import time
     from . import fusion
     indices, depths, probs, cams, images = fusion.load_dense_folder(dense_folder)
     sources = fusion.listed_sources(dense_folder, indices) if fusion_sources == "listed" else None
-    xyz, rgb, _ = fusion.fuse_depth_maps(depths, probs, cams, images, prob_threshold=prob_threshold,
-                                         reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold,
-                                         num_consistent=num_consistent, sources=sources, dedupe=dedupe)
+    plan = fusion.FusionPlan(depths, probs, cams, images, prob_threshold=prob_threshold, reproj_threshold=reproj_threshold,
+                             depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent, sources=sources,
+                             dedupe=dedupe)
+    plan.enqueue()
+    xyz, rgb, _ = plan.result()
     out = os.path.join(point_folder, "consistencyCheck-" + time.strftime("%Y%m%d-%H%M%S"))
     os.makedirs(out, exist_ok=True)
     path = os.path.join(out, "final3d_model.ply")
     fusion.write_ply(path, xyz, rgb)
     print("fused %d views into %d points: %s" % (len(indices), len(xyz), path))
+    if eval_gt:
+        from . import evaluate
+        gt, _ = evaluate.read_ply_points(eval_gt)
+        metrics = evaluate.evaluate_point_clouds(plan.xyz[:len(xyz)], gt, max_dist=eval_max_dist, thresholds=eval_thresholds)
+        with open(os.path.join(out, "metrics.json"), "w") as f:
+            f.write(json.dumps(metrics) + "\n")
+        print("evaluated against %s: %s" % (eval_gt, json.dumps(metrics)))
     return path
 
 
@@ -175,7 +189,20 @@ def main(argv=None):
     ap.add_argument("--no_dedupe", action="store_true", help="--fusion hip: every view independent (witnesses not consumed)")
     ap.add_argument("--fusion_sources", choices=("all", "listed"), default="all",
                     help="--fusion hip: every other view, or the neighbours of pair.txt / covisibility.json in the dense folder")
+    ap.add_argument("--eval_gt", type=str, default=None,
+                    help="--fusion hip: ground-truth PLY; the fused cloud is evaluated against it (metrics.json beside the PLY)")
+    ap.add_argument("--eval_max_dist", type=float, default=20.0, help="--eval_gt: distance cap (outliers at or beyond it)")
+    ap.add_argument("--eval_thresholds", type=str, default="", help="--eval_gt: comma-separated tau for precision / recall / F")
     a = ap.parse_args(argv)
+    eval_thresholds = [float(v) for v in a.eval_thresholds.split(",") if v.strip()]
+    if a.eval_gt:
+        from .evaluate import check_thresholds
+        if a.fusion != "hip":
+            raise SystemExit("--eval_gt needs --fusion hip")
+        try:
+            check_thresholds(eval_thresholds, a.eval_max_dist)
+        except ValueError as e:
+            raise SystemExit("--eval_gt: %s" % e)
     if a.fusion == "hip":
         why = _gpu_ready()
         if why is not None:
@@ -187,7 +214,8 @@ def main(argv=None):
     if a.fusion == "hip":
         print("Run depth map fusion & filter on the GPU")
         return hip_fusion(a.dense_folder, point_folder, a.prob_threshold, a.reproj_threshold, a.depth_rel_threshold,
-                          a.num_consistent, dedupe=not a.no_dedupe, fusion_sources=a.fusion_sources)
+                          a.num_consistent, dedupe=not a.no_dedupe, fusion_sources=a.fusion_sources, eval_gt=a.eval_gt,
+                          eval_max_dist=a.eval_max_dist, eval_thresholds=eval_thresholds)
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")
