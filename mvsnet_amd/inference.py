@@ -550,8 +550,8 @@ def compute_depth_maps(input_dir, config=None, weights=None, device=None, timing
             if gru is not None:
                 gru.add(features, cams_group[gi], depth_num, depth_start, depth_end, rest)
             else:
-                # ADVICE "high": the guide image should be standardised (keep_uint8=False); fixed in a follow-up
-                ref_image = _images_to_device(in_images[0:1], device, keep_uint8=takes_u8) if config.refinement else None
+                # the refinement's guide is the STANDARDISED reference image (predictlib.py:86-88): only tower input may stay uint8
+                ref_image = _images_to_device(in_images[0:1], device, keep_uint8=False) if config.refinement else None
                 m_a, t_b = clock.mark(), time.perf_counter()
                 d, p, _ = pl.get_depth_and_prob_map(None, cams_group[gi][None], depth_start, depth_interval, config, weights,
                                                     depth_num=depth_num, depth_end=depth_end, features=features,

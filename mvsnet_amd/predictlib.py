@@ -53,8 +53,10 @@ def get_depth_and_prob_map(full_images, scaled_cams, depth_start, depth_interval
     raises NameError as shipped (undefined depth_num / depth_end, predictlib.py:95-96); here they
     are explicit arguments (default: config.max_d and start + (D-1)*interval).  `features`
     (N,H/4,W/4,C) skips the 2D towers (used by the per-image feature cache of inference.py); then
-    `ref_image` (1,Himg,Wimg,3) supplies the reference image the refinement tower looks at.
+    `ref_image` (1,Himg,Wimg,3) supplies the STANDARDISED reference image the refinement tower looks at (without it: slice 0
+    of `full_images`, standardised here when the images are the decoded uint8 ones).
     With config.refinement the third result is the residual depth map (predictlib.py:86-92)."""
+    import torch
     from .model import inference_mem, inference_winner_take_all
     D = int(depth_num if depth_num is not None else config.max_d)
     if config.regularization == "3DCNN":
@@ -67,6 +69,9 @@ def get_depth_and_prob_map(full_images, scaled_cams, depth_start, depth_interval
                 raise ValueError("config.refinement needs weights.refine (MVSNetWeights.from_numpy(refine=...))")
             if ref_image is None:
                 ref_image = full_images[:, 0] if full_images.dim() == 5 else full_images[0:1]
+                if ref_image.dtype == torch.uint8:    # decoded images (the HIP towers standardise their own copy): the guide is centred
+                    from .inference import center_images_device
+                    ref_image = center_images_device(ref_image)
             d, residual = depth_refine(d, ref_image.to(d.device), p, D, depth_start, depth_interval, weights.refine,
                                        upsample_depth=config.upsample_before_refinement,
                                        refine_with_confidence=config.refine_with_confidence)

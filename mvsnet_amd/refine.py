@@ -140,6 +140,11 @@ def depth_refine(init_depth_map, image, prob_map, depth_num, depth_start, depth_
     """model.py:753-811.  init_depth_map, prob_map (B,h,w,1); image (B,H,W,3), the centred reference
     image; stereo_image (B,H,W,3) the optional stereo partner (:777-789, training only in the reference).
     Returns (refined_depth_map, residual_depth_map)."""
+    for name, im in (("image", image), ("stereo_image", stereo_image)):
+        if im is not None and not torch.is_floating_point(im):
+            # torch.cat below would promote a decoded 0..255 image silently: refined depths wrong by orders of magnitude
+            raise TypeError("depth_refine: %s is %s; the guide must be the standardised floating-point image the towers see "
+                            "(inference.center_images_device / mvs_data_generation.center_image)" % (name, im.dtype))
     depth_start = float(depth_start); depth_interval = float(depth_interval)
     depth_scale = (depth_start + (float(depth_num) - 1.0) * depth_interval) - depth_start
     norm = (init_depth_map - depth_start) / depth_scale

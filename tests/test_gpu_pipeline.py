@@ -352,6 +352,34 @@ def test_session_pipeline_equals_the_per_reference_view_calls(tmp_path, lib_buil
             assert float((got_d == want_d).mean()) > 0.97          # winner-take-all: a near-tie may flip on a few pixels
 
 
+def test_refined_session_pipeline_equals_the_per_reference_view_calls(tmp_path, lib_built):
+    """The same parity with --refinement, on VALUES: the session (uint8 upload, guide image standardised on the device) writes
+    what one get_depth_and_prob_map call per view gives on the host-standardised float32 images, whose slice 0 is the guide
+    (predictlib.py:86-88).  The refined depth crosses zero with the seeded tower, so the difference is taken relative to the
+    sweep's span; 1e-5 as for the unrefined depth above (device float64 moments against numpy's float32 reductions)."""
+    from mvsnet_amd.inference import build_weights, compute_depth_maps
+    from mvsnet_amd.mvs_data_generation import make_generator
+    from mvsnet_amd import predictlib as pl, preprocess as pp
+    sess = S.write_session(str(tmp_path / "sess"), n_images=4, height=100, width=132, view_num=3, depth_num=24, interval=10.0)
+    cfg = pl.InferenceConfig(input_dir=sess, view_num=3, max_d=24, width=128, height=96, base_image_size=8, refinement=True,
+                             refine_with_confidence=True, output_dir=str(tmp_path / "out"))
+    weights = build_weights(cfg, torch.device("cuda", 0))
+    assert compute_depth_maps(sess, cfg, weights, torch.device("cuda", 0)) == 4
+    gen = make_generator(sess, 3, 128, 96, 24, 1.0, 8, mode="inference", output_scale=0.25)
+    for c in sorted(gen.clusters, key=lambda c_: c_.ref_index):
+        out_images, in_images, out_cams, full_cams, index = gen.prepare(c)
+        d, p, _ = pl.get_depth_and_prob_map(t(in_images)[None], t(out_cams)[None], float(out_cams[0, 1, 3, 0]),
+                                            float(out_cams[0, 1, 3, 1]), cfg, weights, depth_num=int(out_cams[0, 1, 3, 2]),
+                                            depth_end=float(out_cams[0, 1, 3, 3]))
+        want_d, want_p = d.cpu().numpy()[0, :, :, 0], p.cpu().numpy()[0, :, :, 0]
+        got_d = pp.load_pfm(os.path.join(cfg.output_dir, "%d_init.pfm" % index))
+        got_p = pp.load_pfm(os.path.join(cfg.output_dir, "%d_prob.pfm" % index))
+        assert got_d.shape == want_d.shape == (24, 32)
+        assert float(np.abs(want_d - np.clip(want_d, 425.0, 655.0)).max()) > 10.0      # refined: it leaves the swept range
+        assert float(np.mean(np.abs(got_d - want_d))) / 230.0 < 1e-5
+        assert float((np.abs(got_p - want_p) > 1e-3).mean()) < 0.02
+
+
 def test_bench_and_inference_start_their_own_ranks(tmp_path, lib_built):
     """`python bench.py --gpus 2` and `python -m mvsnet_amd.inference --gpus 2` WITHOUT a launcher: the parent stays GPU-less and
     starts one worker per rank (torch.distributed.run); rehearsed on this one-GPU box over gloo with both ranks on cuda:0."""
