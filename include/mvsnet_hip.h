@@ -594,6 +594,31 @@ int mvs_fusion_f32(const float* depth, const float* prob, int V, int H, int W, c
                    float* xyz, uint8_t* rgb, int* view_index, int* pixel_index, int* count, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* Surface normals from depth maps, and the fusion that carries them (csrc/fusion.hip; semantics in mvsnet_amd/fusion.py):
+ *   mvs_depth_normals_f32   per-view normal maps: depth, prob (V,H,W) and tables as for mvs_fusion_f32 (only the B_v part is
+ *                 read); normals (V,H,W,3) float32 in the world frame, unit length and facing the camera, (0,0,0) where a
+ *                 pixel has no normal (invalid, or no usable neighbour along x or along y: a neighbour is usable when it is
+ *                 valid and |d_q - d| < jump_threshold d).  One launch, nothing allocated, nothing synchronised.
+ *   mvs_fusion_normals_f32  mvs_fusion_f32 with normals; the arguments of mvs_fusion_f32 plus
+ *     jump_threshold        the depth-jump limit of the normal maps
+ *     normal_cos_threshold  <= -1: off -- points, order and colours are those of mvs_fusion_f32, bit for bit; otherwise a
+ *                 pixel without a normal is not valid (neither reference pixel nor witness) and a geometrically consistent
+ *                 pair is consistent only when n_r . n_s > normal_cos_threshold (must be < 1)
+ *     normals     (V*H*W,3) float32, capacity as xyz: per point the normalised sum of its reference pixel's normal and its
+ *                 consistent sources' normals (fixed slice order: bitwise reproducible), (0,0,0) when that sum is zero
+ *     workspace   mvs_fusion_normals_workspace_bytes(V, H, W, max_sources, dedupe) bytes, 16-byte aligned (it holds the
+ *                 normal maps as 16 bytes per pixel)
+ * Error codes as mvs_fusion_f32. */
+int mvs_depth_normals_f32(const float* depth, const float* prob, int V, int H, int W, const float* tables, float prob_threshold,
+                          float jump_threshold, float* normals, void* stream);
+size_t mvs_fusion_normals_workspace_bytes(int V, int H, int W, int max_sources, int dedupe);
+int mvs_fusion_normals_f32(const float* depth, const float* prob, int V, int H, int W, const float* tables,
+                           const int* src_offsets, const int* src_index, int max_sources, float prob_threshold,
+                           float reproj_threshold, float depth_rel_threshold, float num_consistent, int dedupe,
+                           float jump_threshold, float normal_cos_threshold, const uint8_t* images, int img_h, int img_w,
+                           float* xyz, uint8_t* rgb, float* normals, int* view_index, int* pixel_index, int* count,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Point-cloud evaluation (csrc/pointcloud.hip; semantics in mvsnet_amd/evaluate.py).  Points are (n,3) float32, n >= 1.
  *
  * Nearest neighbour of every query point in the target cloud, capped at max_dist:

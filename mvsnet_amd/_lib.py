@@ -108,6 +108,10 @@ SIGNATURES = {
     "mvs_regnet_filler_shares": (_i, [C.POINTER(C.c_int)]),
     "mvs_fusion_workspace_bytes": (_sz, [_i] * 5),
     "mvs_fusion_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mvs_depth_normals_f32": (_i, [_p, _p, _i, _i, _i, _p, _f, _f, _p, _p]),
+    "mvs_fusion_normals_workspace_bytes": (_sz, [_i] * 5),
+    "mvs_fusion_normals_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _f, _f, _p, _i, _i, _p, _p, _p, _p, _p,
+                                    _p, _p, _sz, _p]),
     "mvs_nn_workspace_bytes": (_sz, [_i] * 5),
     "mvs_nn_f32": (_i, [_p, _i, _p, _i, _f, _f, _f, _f, _i, _i, _i, _f, _p, _p, _p, _sz, _p]),
     "mvs_nn_query_f32": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),

@@ -16,7 +16,11 @@ points_mvsnet/consistencyCheck-<YYYYmmdd-HHMMSS>/final3d_model.ply, the path the
     python -m mvsnet_amd.depthfusion --dense_folder <dir> --fusion hip [--reproj_threshold 1.0]
         [--depth_rel_threshold 0.01] [--no_dedupe] [--fusion_sources {all,listed}]
         [--eval_gt G.ply [--eval_max_dist 20] [--eval_thresholds 0.5,1,2]]
-and, with --eval_gt, evaluates that cloud against a ground-truth PLY on the GPU (mvsnet_amd.evaluate) into metrics.json beside it.
+        [--normals] [--normal_angle_threshold DEG] [--jump_threshold 0.05] [--write_normal_maps]
+--normals estimates surface normals from the depth maps on the GPU and writes the PLY as x y z nx ny nz red green blue
+(fusibile's vertex layout); --normal_angle_threshold (implies --normals) also rejects pairs whose normals differ by more;
+--write_normal_maps writes depths_mvsnet/<idx>_normal.pfm (colour PFM, camera frame).  The Gipuma hand-off keeps the
+reference's constant fake normals.  And, with --eval_gt, evaluates that cloud against a ground-truth PLY on the GPU (mvsnet_amd.evaluate) into metrics.json beside it.
 File formats are byte-compatible with the reference's writers (.dmb: int32 header 1,H,W,C +
 float32 data in the reference's element order).
 """
@@ -133,8 +137,10 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
 
 
 def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent,
-               dedupe=True, fusion_sources="all", eval_gt=None, eval_max_dist=20.0, eval_thresholds=()):
-    """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply.
+               dedupe=True, fusion_sources="all", eval_gt=None, eval_max_dist=20.0, eval_thresholds=(), normals=False,
+               normal_angle_threshold=None, jump_threshold=0.05, write_normal_maps=False):
+    """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply
+    (with normals: x y z nx ny nz red green blue; write_normal_maps: depths_mvsnet/<idx>_normal.pfm, camera frame).
     With eval_gt (a PLY), the fused cloud is evaluated against it on the device (mvsnet_amd.evaluate) and the metrics are
     written to metrics.json next to the PLY."""
     import json
@@ -144,13 +150,20 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
     sources = fusion.listed_sources(dense_folder, indices) if fusion_sources == "listed" else None
     plan = fusion.FusionPlan(depths, probs, cams, images, prob_threshold=prob_threshold, reproj_threshold=reproj_threshold,
                              depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent, sources=sources,
-                             dedupe=dedupe)
+                             dedupe=dedupe, normals=normals, normal_angle_threshold=normal_angle_threshold,
+                             jump_threshold=jump_threshold)
     plan.enqueue()
-    xyz, rgb, _ = plan.result()
+    res = plan.result(with_normals=plan.normals)
+    xyz, rgb, nrm = res[0], res[1], (res[3] if plan.normals else None)
+    if write_normal_maps:
+        maps = fusion.estimate_normals(plan.depth, plan.prob, cams, prob_threshold=prob_threshold, jump_threshold=jump_threshold,
+                                       frame="camera")
+        for i, m in zip(indices, maps):
+            write_pfm(os.path.join(dense_folder, "depths_mvsnet", "%d_normal.pfm" % i), m)
     out = os.path.join(point_folder, "consistencyCheck-" + time.strftime("%Y%m%d-%H%M%S"))
     os.makedirs(out, exist_ok=True)
     path = os.path.join(out, "final3d_model.ply")
-    fusion.write_ply(path, xyz, rgb)
+    fusion.write_ply(path, xyz, rgb, nrm)
     print("fused %d views into %d points: %s" % (len(indices), len(xyz), path))
     if eval_gt:
         from . import evaluate
@@ -193,7 +206,26 @@ def main(argv=None):
                     help="--fusion hip: ground-truth PLY; the fused cloud is evaluated against it (metrics.json beside the PLY)")
     ap.add_argument("--eval_max_dist", type=float, default=20.0, help="--eval_gt: distance cap (outliers at or beyond it)")
     ap.add_argument("--eval_thresholds", type=str, default="", help="--eval_gt: comma-separated tau for precision / recall / F")
+    ap.add_argument("--normals", action="store_true", help="--fusion hip: estimate normals, PLY vertices x y z nx ny nz r g b")
+    ap.add_argument("--normal_angle_threshold", type=float, default=None,
+                    help="--fusion hip: pairs whose normals differ by this many degrees or more are inconsistent (implies --normals)")
+    ap.add_argument("--jump_threshold", type=float, default=None,
+                    help="--fusion hip: relative depth jump beyond which a neighbour is not used for a normal (0.05)")
+    ap.add_argument("--write_normal_maps", action="store_true",
+                    help="--fusion hip: write depths_mvsnet/<idx>_normal.pfm (colour PFM, camera frame)")
     a = ap.parse_args(argv)
+    if a.fusion != "hip":
+        for flag, given in (("--normals", a.normals), ("--normal_angle_threshold", a.normal_angle_threshold is not None),
+                            ("--jump_threshold", a.jump_threshold is not None), ("--write_normal_maps", a.write_normal_maps)):
+            if given:
+                raise SystemExit("%s needs --fusion hip" % flag)
+    else:
+        from .fusion import check_jump_threshold, normal_cos_threshold
+        try:
+            normal_cos_threshold(a.normal_angle_threshold)
+            check_jump_threshold(0.05 if a.jump_threshold is None else a.jump_threshold)
+        except ValueError as e:
+            raise SystemExit(str(e))
     eval_thresholds = [float(v) for v in a.eval_thresholds.split(",") if v.strip()]
     if a.eval_gt:
         from .evaluate import check_thresholds
@@ -215,7 +247,10 @@ def main(argv=None):
         print("Run depth map fusion & filter on the GPU")
         return hip_fusion(a.dense_folder, point_folder, a.prob_threshold, a.reproj_threshold, a.depth_rel_threshold,
                           a.num_consistent, dedupe=not a.no_dedupe, fusion_sources=a.fusion_sources, eval_gt=a.eval_gt,
-                          eval_max_dist=a.eval_max_dist, eval_thresholds=eval_thresholds)
+                          eval_max_dist=a.eval_max_dist, eval_thresholds=eval_thresholds, normals=a.normals,
+                          normal_angle_threshold=a.normal_angle_threshold,
+                          jump_threshold=0.05 if a.jump_threshold is None else a.jump_threshold,
+                          write_normal_maps=a.write_normal_maps)
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")
