@@ -508,9 +508,7 @@ int launch_s1_fuse2(const ConvArgs& a0, const Fuse2Args& fa, hipStream_t st) {
 
 }  // namespace
 
-// test hook: MVS_GENERIC_C8=1 keeps the 32 -> 8 layer on the generic kernel (A/B timing, parity)
-
-static int conv_dispatch(ConvArgs& a, int Cin, int Cout, int stride, hipStream_t st) {
+int mvs_conv3d_dispatch(ConvArgs& a, int Cin, int Cout, int stride, hipStream_t st) {
     if (stride == 1) {
         if (Cout == 1) return mvs_conv3d_out_launch(a, Cin, st);
         if (Cin == 1) return mvs_conv3d_in1_launch(a, Cout, st);     // input gradient of the one-channel output layer
@@ -539,41 +537,10 @@ static int conv_dispatch(ConvArgs& a, int Cin, int Cout, int stride, hipStream_t
     return mvs_conv3d_s2_mfma(a, Cin, Cout, st);
 }
 
-int mvs_conv3d_mfma(const float* x, const float* xs, const float* xb, const float* x2,
-                    const float* x2s, const float* x2b, const float* w, int D, int H, int W,
-                    int Cin, int Cout, int stride, float* y, double* stats, hipStream_t st) {
-    ConvArgs a{x, xs, xb, x2, x2s, x2b, w, y, stats, D, H, W, Cout, 0, 0, 0, 0, {}, {}, nullptr, nullptr};
-    return conv_dispatch(a, Cin, Cout, stride, st);
-}
-
-int mvs_deconv3d_mfma(const float* x, const float* xs, const float* xb, const float* x2,
-                      const float* x2s, const float* x2b, const float* w, int D, int H, int W,
-                      int Cin, int Cout, float* y, double* stats, hipStream_t st) {
-    ConvArgs a{x, xs, xb, x2, x2s, x2b, w, y, stats, D, H, W, Cout, 0, 0, 0, 0, {}, {}, nullptr, nullptr};
-    return mvs_deconv3d_mfma_launch(a, Cin, Cout, st);
-}
-
-// Variants taking the producers' raw BatchNorm sums (regnet.hip): no bn_finalize launch in between.
-int mvs_conv3d_mfma_bn(const float* x, const BnSrc& bn, const float* x2, const BnSrc& bn2,
-                       const float* w, const float* wprep, const unsigned short* wprep_bf, int D, int H,
-                       int W, int Cin, int Cout, int stride, float* y, double* stats, hipStream_t st, int stats_slots) {
-    ConvArgs a{x, nullptr, nullptr, x2, nullptr, nullptr, w, y, stats, D, H, W, Cout, 0, 0, 0, 0, bn, bn2, wprep, wprep_bf, stats_slots};
-    return conv_dispatch(a, Cin, Cout, stride, st);
-}
-
-int mvs_deconv3d_mfma_bn(const float* x, const BnSrc& bn, const float* x2, const BnSrc& bn2,
-                         const float* w, const float* wprep, int D, int H, int W, int Cin, int Cout,
-                         float* y, double* stats, hipStream_t st, int stats_slots) {
-    ConvArgs a{x, nullptr, nullptr, x2, nullptr, nullptr, w, y, stats, D, H, W, Cout, 0, 0, 0, 0, bn, bn2, wprep, nullptr, stats_slots};
-    return mvs_deconv3d_mfma_launch(a, Cin, Cout, st);
-}
-
 // 3dconv1_1 (x -> y, 16 -> 16, stride 1) and 3dconv2_0 (x -> y2, 16 -> 32, stride 2) over the same BN + ReLU input in one pass
-int mvs_conv3d_s1s2_16_bn(const float* x, const BnSrc& bn, const float* w, const float* wprep, int D, int H, int W, float* y,
-                          double* stats, const float* w2, float* y2, double* stats2, hipStream_t st, int stats_slots) {
+int mvs_conv3d_s1_fuse2_launch(const ConvArgs& a, const float* w2, float* y2, double* stats2, hipStream_t st) {
     if (mvs_hook(MVS_HOOK_CONV_NO_FUSE2)) return MVS_E_SHAPE;      // test hook: the caller then runs the two layers apart (tests/test_gpu_parity.py)
-    ConvArgs a{x, nullptr, nullptr, nullptr, nullptr, nullptr, w, y, stats, D, H, W, 16, 0, 0, 0, 0, bn, BnSrc{}, wprep, nullptr, stats_slots};
-    return launch_s1_fuse2(a, Fuse2Args{w2, y2, stats2, stats_slots}, st);
+    return launch_s1_fuse2(a, Fuse2Args{w2, y2, stats2, a.stats_slots}, st);
 }
 
 // ---- weight pre-layout (run once per weight set, mvs_regnet_prepare_f32) ---------------------------

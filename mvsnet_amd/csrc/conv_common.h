@@ -64,19 +64,26 @@ __device__ __forceinline__ void bn_affine4_from(const BnSrc& b, const BnSums4& r
     sh = make_float4(t[0], t[1], t[2], t[3]);
 }
 
+// A kernel argument: the order, types and size of the fields are fixed.  Every field defaults to null / 0; the host builds one
+// with conv_args() below and sets what else a launch means by name (planes_per_wg and the pads are the launchers').
 struct ConvArgs {
-    const float* x; const float* xs; const float* xb;      // input + producer BN affine (or null)
-    const float* x2; const float* x2s; const float* x2b;   // optional additive skip input
-    const float* w;                                         // TensorFlow kernel layout
-    float* y;                                               // raw (pre-BN) output
-    double* stats;                                          // (2,CoutTotal) float64 sums or null
-    int D, H, W, cout_total, planes_per_wg;
-    int pd, ph, pw;                                         // SAME pad_before per axis (stride 2)
-    BnSrc bn, bn2;                                          // alternative to xs/xb, x2s/x2b (stats given)
-    const float* wprep;                                     // weights already in the kernel's LDS order, or null
-    const unsigned short* wprep_bf;                         // bf16 hi|lo split weights (opt-in bf16x3 path), or null
-    int stats_slots;                                        // > 1: stats is (slots, 2, CoutTotal) partial rows, see conv_stats_row
+    const float* x = nullptr; const float* xs = nullptr; const float* xb = nullptr;      // input + producer BN affine (or null)
+    const float* x2 = nullptr; const float* x2s = nullptr; const float* x2b = nullptr;   // optional additive skip input
+    const float* w = nullptr;                               // TensorFlow kernel layout
+    float* y = nullptr;                                     // raw (pre-BN) output
+    double* stats = nullptr;                                // (2,CoutTotal) float64 sums or null
+    int D = 0, H = 0, W = 0, cout_total = 0, planes_per_wg = 0;
+    int pd = 0, ph = 0, pw = 0;                             // SAME pad_before per axis (stride 2)
+    BnSrc bn = {}, bn2 = {};                                // alternative to xs/xb, x2s/x2b (stats given)
+    const float* wprep = nullptr;                           // weights already in the kernel's LDS order, or null
+    const unsigned short* wprep_bf = nullptr;               // bf16 hi|lo split weights (opt-in bf16x3 path), or null
+    int stats_slots = 0;                                    // > 1: stats is (slots, 2, CoutTotal) partial rows, see conv_stats_row
 };
+static inline ConvArgs conv_args(const float* x, const float* w, float* y, double* stats, int D, int H, int W, int cout_total) {
+    ConvArgs a;
+    a.x = x; a.w = w; a.y = y; a.stats = stats; a.D = D; a.H = H; a.W = W; a.cout_total = cout_total;
+    return a;
+}
 
 // BatchNorm sums go to memory-side float64 atomics.  With every workgroup of a layer adding into the same 2*C doubles the
 // atomics cost ~5 us at the end of each 240..960-workgroup layer (measured by leaving them out: the low-resolution chain
@@ -191,6 +198,22 @@ __device__ __forceinline__ void load_prepared_weights(float* wl, const float* wp
 
 // launchers implemented in the kernel files; MVS_E_SHAPE when the shape is outside their tiling
 constexpr int MVS_BN_SLOTS_MAX = 8;      // partial rows per BatchNorm layer in the regulariser's workspace
+// stride 1 / 2 by (Cin, Cout, stride): picks the MFMA kernel (conv3d_mfma.hip) and sets the stride-2 pads in `a`
+int mvs_conv3d_dispatch(ConvArgs& a, int Cin, int Cout, int stride, hipStream_t st);
+// 3dconv1_1 (a: 16 -> 16, stride 1) and 3dconv2_0 (-> y2, 16 -> 32, stride 2; its sums take a.stats_slots rows too) over the same
+// BN + ReLU input in one pass (conv3d_mfma.hip, FUSE2)
+int mvs_conv3d_s1_fuse2_launch(const ConvArgs& a, const float* w2, float* y2, double* stats2, hipStream_t st);
+int mvs_conv_weight_layout(const float* w, int kind, int Cin, int Cout, float* out, hipStream_t st);      // conv3d_mfma.hip
+// shape-generic scalar kernels (conv3d_scalar.hip): any shape, producers' BatchNorm as finalised (scale, shift)
+int mvs_conv3d_scalar(const float* x, const float* xs, const float* xb, const float* x2, const float* x2s, const float* x2b,
+                      const float* w, int D, int H, int W, int Cin, int Cout, int stride, float* y, double* stats, hipStream_t st);
+int mvs_deconv3d_scalar(const float* x, const float* xs, const float* xb, const float* x2, const float* x2s, const float* x2b,
+                        const float* w, int D, int H, int W, int Cin, int Cout, float* y, double* stats, hipStream_t st);
+// plane homographies + zero-fill of `zero_n` doubles in one launch (homography.hip)
+int mvs_homography_transforms_zero(const float* cams, int view_num, int depth_num, float depth_start, float depth_interval,
+                                   float depth_end, int inverse_depth, float* transforms, double* zero, int zero_n, hipStream_t st);
+// one side stream + fork / join events of the caller's stream set (gru.hip, mvs_gru_prepare); false without a set
+bool mvs_stream_set_side(hipStream_t caller, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);
 int mvs_conv3d_s2_mfma(const ConvArgs& a, int Cin, int Cout, hipStream_t st);
 int mvs_deconv3d_mfma_launch(const ConvArgs& a, int Cin, int Cout, hipStream_t st);
 int mvs_conv3d_out_launch(const ConvArgs& a, int Cin, hipStream_t st);

@@ -1,82 +1,9 @@
-// Host-side composition: conv dispatch (scalar vs MFMA), the RegNetUS0 3D U-Net launch sequence
-// (mvsnet/cnn_wrapper/mvsnetworks.py:122-158) and library bookkeeping entry points.
-// No kernels here; every launch goes to the caller's stream and nothing allocates or syncs.
+// Host-side composition: the single-layer entry points (scalar vs MFMA), the RegNetUS0 3D U-Net as a layer table plus its
+// launch sequence (mvsnet/cnn_wrapper/mvsnetworks.py:122-158), its workspace and weight preparation, and features -> depth in
+// one call.  One small fold kernel here; every launch goes to the caller's stream and nothing allocates or syncs.
 #include "conv_common.h"
-#include <cstdlib>
-#include <mutex>
-
-// scalar path (conv3d_scalar.hip)
-int mvs_conv3d_scalar(const float*, const float*, const float*, const float*, const float*,
-                      const float*, const float*, int, int, int, int, int, int, float*, double*,
-                      hipStream_t);
-int mvs_deconv3d_scalar(const float*, const float*, const float*, const float*, const float*,
-                        const float*, const float*, int, int, int, int, int, float*, double*,
-                        hipStream_t);
-// MFMA path (conv3d_mfma.hip); returns MVS_E_SHAPE when the shape is outside its tiling
-int mvs_conv3d_mfma(const float*, const float*, const float*, const float*, const float*,
-                    const float*, const float*, int, int, int, int, int, int, float*, double*,
-                    hipStream_t);
-int mvs_deconv3d_mfma(const float*, const float*, const float*, const float*, const float*,
-                      const float*, const float*, int, int, int, int, int, float*, double*,
-                      hipStream_t);
-// same, taking the producers' raw BatchNorm sums instead of a finalised (scale, shift)
-int mvs_conv3d_s1s2_16_bn(const float* x, const BnSrc& bn, const float* w, const float* wprep, int D, int H, int W, float* y,
-                          double* stats, const float* w2, float* y2, double* stats2, hipStream_t st, int stats_slots);
-int mvs_conv3d_mfma_bn(const float* x, const BnSrc& bn, const float* x2, const BnSrc& bn2,
-                       const float* w, const float* wprep, const unsigned short* wprep_bf, int D, int H,
-                       int W, int Cin, int Cout, int stride, float* y, double* stats, hipStream_t st, int stats_slots);
-int mvs_deconv3d_mfma_bn(const float* x, const BnSrc& bn, const float* x2, const BnSrc& bn2,
-                         const float* w, const float* wprep, int D, int H, int W, int Cin, int Cout,
-                         float* y, double* stats, hipStream_t st, int stats_slots);
-int mvs_conv_weight_layout(const float* w, int kind, int Cin, int Cout, float* out, hipStream_t st);
-
-bool mvs_stream_set_side(hipStream_t caller, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);      // gru.hip
-
-static int g_conv_impl = MVS_CONV_IMPL_AUTO;
-
-extern "C" int mvs_abi_version(void) { return MVS_ABI_VERSION; }
-
-extern "C" const char* mvs_error_string(int code) {
-    if (code == 0) return "success";
-    if (code == MVS_E_BADARG) return "mvsnet_hip: bad argument (null pointer or non-positive size)";
-    if (code == MVS_E_SHAPE) return "mvsnet_hip: shape not supported by this kernel";
-    if (code == MVS_E_WORKSPACE) return "mvsnet_hip: workspace too small";
-    if (code == MVS_E_NO_SLOT) return "mvsnet_hip: all 16 stream sets of mvs_gru_prepare are in use (mvs_gru_release frees one); the sweep still runs, on the caller's stream alone";
-    if (code == MVS_E_NOT_PREPARED) return "mvsnet_hip: no side streams for this caller stream (call mvs_gru_prepare outside hipGraph capture first)";
-    if (code > 0) return hipGetErrorString((hipError_t)code);
-    return "mvsnet_hip: unknown error";
-}
-
-extern "C" int mvs_set_conv_impl(int impl) {
-    if (impl < MVS_CONV_IMPL_AUTO || impl > MVS_CONV_IMPL_BF16X3) return MVS_E_BADARG;
-    g_conv_impl = impl;
-    return 0;
-}
-extern "C" int mvs_get_conv_impl(void) { return g_conv_impl; }
-
-// test / measurement hooks (include/mvsnet_hip.h): the only switches of the library; nothing is read from the environment
-std::atomic<int> mvs_hooks[MVS_HOOK_COUNT] = {{-1}, {0}, {0}, {0}, {0}, {128}, {1}, {0}, {0}, {0}};
-extern "C" int mvs_set_test_hook(int id, int value) {
-    bool ok = false;
-    switch (id) {
-        case MVS_HOOK_CV_TILE_ROWS_LOG2: ok = value >= -1 && value <= 3; break;
-        case MVS_HOOK_CONV_NO_SPAN: case MVS_HOOK_CONV_NO_FUSE2: case MVS_HOOK_GRU_ONE_STREAM: case MVS_HOOK_UNET_PERSISTENT:
-        case MVS_HOOK_REGNET_SIDE_BRANCH:
-            ok = value == 0 || value == 1; break;
-        case MVS_HOOK_UNET_GRID: ok = value >= 0 && value <= 65536; break;
-        case MVS_HOOK_FUSE2_PLANES: ok = value >= 0 && value <= 65536 && (value & 1) == 0; break;
-        case MVS_HOOK_S2_PLANES: ok = value >= 0 && value <= 65536; break;
-        case MVS_HOOK_GRU_PRODUCER_THREADS: ok = value == 64 || value == 128 || value == 192 || value == 256; break;
-        default: break;
-    }
-    if (!ok) return MVS_E_BADARG;
-    mvs_hooks[id].store(value, std::memory_order_relaxed);
-    return 0;
-}
-extern "C" int mvs_get_test_hook(int id) {
-    if (id < 0 || id >= MVS_HOOK_COUNT) return MVS_E_BADARG;
-    return mvs_hooks[id].load(std::memory_order_relaxed);
-}
+#include "profile.h"
+#include <initializer_list>
 
 extern "C" int mvs_conv3d_f32(const float* x, const float* xs, const float* xb, const float* x2,
                               const float* x2s, const float* x2b, const float* w, int D, int H,
@@ -86,9 +13,12 @@ extern "C" int mvs_conv3d_f32(const float* x, const float* xs, const float* xb, 
     MVS_CHECK_ARG((xs == nullptr) == (xb == nullptr) && (x2s == nullptr) == (x2b == nullptr));
     MVS_CHECK_ARG(stride == 1 || stride == 2);
     hipStream_t st = mvs_stream(stream);
-    if (g_conv_impl != MVS_CONV_IMPL_SCALAR) {
-        int rc = mvs_conv3d_mfma(x, xs, xb, x2, x2s, x2b, w, D, H, W, Cin, Cout, stride, y, stats, st);
-        if (rc != MVS_E_SHAPE || g_conv_impl == MVS_CONV_IMPL_MFMA) return rc;
+    const int impl = mvs_get_conv_impl();
+    if (impl != MVS_CONV_IMPL_SCALAR) {
+        ConvArgs a = conv_args(x, w, y, stats, D, H, W, Cout);
+        a.xs = xs; a.xb = xb; a.x2 = x2; a.x2s = x2s; a.x2b = x2b;
+        int rc = mvs_conv3d_dispatch(a, Cin, Cout, stride, st);
+        if (rc != MVS_E_SHAPE || impl == MVS_CONV_IMPL_MFMA) return rc;
     }
     return mvs_conv3d_scalar(x, xs, xb, x2, x2s, x2b, w, D, H, W, Cin, Cout, stride, y, stats, st);
 }
@@ -99,9 +29,12 @@ extern "C" int mvs_deconv3d_f32(const float* x, const float* xs, const float* xb
     MVS_CHECK_ARG(x && w && y && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
     MVS_CHECK_ARG((xs == nullptr) == (xb == nullptr) && (x2s == nullptr) == (x2b == nullptr));
     hipStream_t st = mvs_stream(stream);
-    if (g_conv_impl != MVS_CONV_IMPL_SCALAR) {
-        int rc = mvs_deconv3d_mfma(x, xs, xb, x2, x2s, x2b, w, D, H, W, Cin, Cout, y, stats, st);
-        if (rc != MVS_E_SHAPE || g_conv_impl == MVS_CONV_IMPL_MFMA) return rc;
+    const int impl = mvs_get_conv_impl();
+    if (impl != MVS_CONV_IMPL_SCALAR) {
+        ConvArgs a = conv_args(x, w, y, stats, D, H, W, Cout);
+        a.xs = xs; a.xb = xb; a.x2 = x2; a.x2s = x2s; a.x2b = x2b;
+        int rc = mvs_deconv3d_mfma_launch(a, Cin, Cout, st);
+        if (rc != MVS_E_SHAPE || impl == MVS_CONV_IMPL_MFMA) return rc;
     }
     return mvs_deconv3d_scalar(x, xs, xb, x2, x2s, x2b, w, D, H, W, Cin, Cout, y, stats, st);
 }
@@ -110,101 +43,8 @@ extern "C" int mvs_conv3d_pair_f32(const float* x, const float* w1, const float*
                                    int Cin, int Cout1, int Cout2, float* y1, double* stats1,
                                    float* y2, double* stats2, void* stream) {
     MVS_CHECK_ARG(x && w1 && w2 && y1 && y2 && D > 0 && H > 0 && W > 0);
-    if (Cin != 32 || Cout1 != 8 || Cout2 != 16 || g_conv_impl == MVS_CONV_IMPL_SCALAR) return MVS_E_SHAPE;
-    ConvArgs a{x, nullptr, nullptr, nullptr, nullptr, nullptr, w1, y1, stats1, D, H, W, Cout1, 0, 0, 0, 0, {}, {}, nullptr, nullptr};
-    return mvs_conv3d_c8_s2_launch(a, w2, y2, stats2, mvs_stream(stream));
-}
-
-// ---- live timing of the dominant kernel (bench.py's roofline object) --------------------------------
-// When enabled, every RegNetUS0 run brackets its first launch -- the fused 3dconv0_1 + 3dconv1_0 pass,
-// ~45 % of a depth map -- with a pair of HIP events on the caller's stream.  Not for graph capture.
-namespace {
-// (nslot, n) partial rows of BatchNorm sums -> row 0 holds the total, the other rows zero
-__global__ void bn_fold_rows_kernel(double* stats, int nslot, int n) {
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        double t = stats[j];
-        for (int r = 1; r < nslot; ++r) { t += stats[(size_t)r * n + j]; stats[(size_t)r * n + j] = 0.0; }
-        stats[j] = t;
-    }
-}
-}  // namespace
-
-namespace {
-struct DominantProfile { bool on = false; hipEvent_t ev[64][2]; int used = 0; int created = 0; } g_prof;
-}
-extern "C" int mvs_profile_dominant(int enable) {
-    g_prof.on = enable != 0;
-    g_prof.used = 0;
-    return 0;
-}
-extern "C" int mvs_profile_dominant_ms(double* avg_ms, int* count) {
-    MVS_CHECK_ARG(avg_ms && count);
-    double sum = 0.0;
-    for (int i = 0; i < g_prof.used; ++i) {
-        hipError_t e = hipEventSynchronize(g_prof.ev[i][1]);
-        if (e != hipSuccess) return (int)e;
-        float ms = 0.f;
-        if ((e = hipEventElapsedTime(&ms, g_prof.ev[i][0], g_prof.ev[i][1])) != hipSuccess) return (int)e;
-        sum += ms;
-    }
-    *count = g_prof.used;
-    *avg_ms = g_prof.used ? sum / g_prof.used : 0.0;
-    g_prof.used = 0;
-    return 0;
-}
-
-// ---- per-layer timing (bench.py's roofline_kernels rows) --------------------------------------------
-namespace {
-struct LayerProfile { bool on = false; hipEvent_t ev[32][11][2]; bool hit[32][11]; int used = 0; int created = 0; } g_lprof;
-}
-extern "C" int mvs_profile_layers(int enable) {
-    g_lprof.on = enable != 0;
-    g_lprof.used = 0;
-    return 0;
-}
-extern "C" int mvs_profile_layers_ms(double* avg_ms11, int* count) {
-    MVS_CHECK_ARG(avg_ms11 && count);
-    for (int l = 0; l < 11; ++l) avg_ms11[l] = 0.0;
-    for (int i = 0; i < g_lprof.used; ++i)
-        for (int l = 0; l < 11; ++l) {
-            if (!g_lprof.hit[i][l]) continue;
-            hipError_t e = hipEventSynchronize(g_lprof.ev[i][l][1]);
-            if (e != hipSuccess) return (int)e;
-            float ms = 0.f;
-            if ((e = hipEventElapsedTime(&ms, g_lprof.ev[i][l][0], g_lprof.ev[i][l][1])) != hipSuccess) return (int)e;
-            avg_ms11[l] += ms;
-        }
-    *count = g_lprof.used;
-    if (g_lprof.used) for (int l = 0; l < 11; ++l) avg_ms11[l] /= g_lprof.used;
-    g_lprof.used = 0;
-    return 0;
-}
-
-// ---- stage timing of mvs_depth_from_features_f32 (bench.py's roofline_kernels: the split of the TIMED path) ------------
-namespace {
-struct StageProfile { bool on = false; hipEvent_t ev[32][4]; int used = 0; int created = 0; } g_sprof;
-}
-extern "C" int mvs_profile_stages(int enable) {
-    g_sprof.on = enable != 0;
-    g_sprof.used = 0;
-    return 0;
-}
-extern "C" int mvs_profile_stages_ms(double* avg_ms3, int* count) {
-    MVS_CHECK_ARG(avg_ms3 && count);
-    for (int l = 0; l < 3; ++l) avg_ms3[l] = 0.0;
-    for (int i = 0; i < g_sprof.used; ++i) {
-        hipError_t e = hipEventSynchronize(g_sprof.ev[i][3]);
-        if (e != hipSuccess) return (int)e;
-        for (int l = 0; l < 3; ++l) {
-            float ms = 0.f;
-            if ((e = hipEventElapsedTime(&ms, g_sprof.ev[i][l], g_sprof.ev[i][l + 1])) != hipSuccess) return (int)e;
-            avg_ms3[l] += ms;
-        }
-    }
-    *count = g_sprof.used;
-    if (g_sprof.used) for (int l = 0; l < 3; ++l) avg_ms3[l] /= g_sprof.used;
-    g_sprof.used = 0;
-    return 0;
+    if (Cin != 32 || Cout1 != 8 || Cout2 != 16 || mvs_get_conv_impl() == MVS_CONV_IMPL_SCALAR) return MVS_E_SHAPE;
+    return mvs_conv3d_c8_s2_launch(conv_args(x, w1, y1, stats1, D, H, W, Cout1), w2, y2, stats2, mvs_stream(stream));
 }
 
 // ---- RegNetUS0 -----------------------------------------------------------------------------------
@@ -222,37 +62,85 @@ extern "C" int mvs_regnet_filler_shares(int* permille3) {
 
 namespace {
 
-constexpr int N_BN = 10;   // layers with BatchNorm, order: 1_0 2_0 3_0 0_1 1_1 2_1 3_1 4_0 5_0 6_0
-enum { L10, L20, L30, L01, L11, L21, L31, L40, L50, L60, L62 };
+// ---- the layer table: everything else about the network's shape is derived from it ----------------
+constexpr int N_LAYERS = 11, N_BN = 10;      // all layers but the output conv have BatchNorm
+enum { L10, L20, L30, L01, L11, L21, L31, L40, L50, L60, L62 };      // order of the weights array
+enum { S1 = 0, S2 = 1, UP = 2 };             // stride 1, stride 2, transposed: conv_coutg's kinds
+constexpr int COST = 0, ONE = 0;             // ci: the cost volume's cin;  co: the single output channel
+struct LayerRow {
+    int kind;
+    int level;       // resolution of the input: (D, H, W) >> level
+    int ci, co;      // channels in multiples of base (or COST / ONE)
+    int p1, p2;      // producers: in = BN+ReLU(p1) [+ BN+ReLU(p2)]; -1 = the raw cost volume / none
+};
+constexpr LayerRow NET[N_LAYERS] = {
+    // encoder (mvsnetworks.py:130-136)
+    /* 3dconv1_0 */ {S2, 0, COST, 2, -1, -1},
+    /* 3dconv2_0 */ {S2, 1, 2, 4, L10, -1},
+    /* 3dconv3_0 */ {S2, 2, 4, 8, L20, -1},
+    // same-resolution branches, only needed by the decoder (mvsnetworks.py:138-141)
+    /* 3dconv0_1 */ {S1, 0, COST, 1, -1, -1},
+    /* 3dconv1_1 */ {S1, 1, 2, 2, L10, -1},
+    /* 3dconv2_1 */ {S1, 2, 4, 4, L20, -1},
+    /* 3dconv3_1 */ {S1, 3, 8, 8, L30, -1},
+    // decoder with additive skips (mvsnetworks.py:146-157)
+    /* 3dconv4_0 */ {UP, 3, 8, 4, L31, -1},
+    /* 3dconv5_0 */ {UP, 2, 4, 2, L40, L21},
+    /* 3dconv6_0 */ {UP, 1, 2, 1, L50, L11},
+    // output conv, no BN / ReLU / bias (mvsnetworks.py:158)
+    /* 3dconv6_2 */ {S1, 0, 1, ONE, L60, L01},
+};
+constexpr int out_level(int i) { return NET[i].level + (NET[i].kind == S2) - (NET[i].kind == UP); }
+constexpr int widest() { int m = 0; for (const LayerRow& r : NET) m = r.co > m ? r.co : m; return m; }
+constexpr int CMAX = widest();               // widest layer, in multiples of base
+
+// doubles of the BatchNorm sums: N_BN x MVS_BN_SLOTS_MAX x 2 x cmax (partial rows per layer, conv_common.h: conv_stats_row)
+size_t stats_doubles(int b) { return (size_t)N_BN * MVS_BN_SLOTS_MAX * 2 * CMAX * b; }
+
+// the table at one (cin, base): channel counts, and where each layer's pre-laid-out weights live
+struct Net {
+    int ci[N_LAYERS], co[N_LAYERS];
+    size_t woff[N_LAYERS], wtotal;           // floats; the bf16 hi|lo layouts follow the fp32 ones at wtotal + woff
+    bool ok[N_LAYERS], bf[N_LAYERS];         // has an MFMA weight layout / a bf16x3 one
+};
+Net net_of(int cin, int b) {
+    Net n;
+    size_t off = 0;
+    for (int i = 0; i < N_LAYERS; ++i) {
+        const int kind = NET[i].kind, ci = NET[i].ci == COST ? cin : NET[i].ci * b, co = NET[i].co == ONE ? 1 : NET[i].co * b;
+        n.ci[i] = ci; n.co[i] = co; n.woff[i] = off;
+        n.ok[i] = (i != L62) && (ci % 4 == 0) && conv_coutg(kind, ci, co) != 0;
+        n.bf[i] = n.ok[i] && kind == S1 && mvs_conv3d_bf16x3_supported(ci, co);
+        off += (size_t)27 * ci * co;
+    }
+    n.wtotal = off;
+    return n;
+}
 
 struct RegnetWs {
     float* y[N_BN];        // raw (pre-BN) outputs
     float* scale[N_BN];
     float* shift[N_BN];
-    double* stats;         // N_BN x MVS_BN_SLOTS_MAX x 2 x cmax (partial rows per layer, conv_common.h: conv_stats_row)
+    double* stats;         // stats_doubles(b)
     size_t bytes;
 };
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-RegnetWs carve(char* base, int D, int H, int W, int cin, int b) {
-    (void)cin;
-    const size_t v0 = (size_t)D * H * W, v1 = v0 / 8, v2 = v1 / 8, v3 = v2 / 8;
-    const size_t vox[N_BN] = {v1, v2, v3, v0, v1, v2, v3, v2, v1, v0};
-    const int ch[N_BN] = {2 * b, 4 * b, 8 * b, b, 2 * b, 4 * b, 8 * b, 4 * b, 2 * b, b};
-    const int cmax = 8 * b;
+RegnetWs carve(char* base, int D, int H, int W, int b) {
+    const size_t v0 = (size_t)D * H * W;
     size_t off = 0;
     RegnetWs w;
     for (int i = 0; i < N_BN; ++i) {
         w.y[i] = (float*)(base ? base + off : nullptr);
-        off += align256(vox[i] * ch[i] * sizeof(float));
+        off += align256((v0 >> (3 * out_level(i))) * NET[i].co * b * sizeof(float));
     }
     for (int i = 0; i < N_BN; ++i) {
-        w.scale[i] = (float*)(base ? base + off : nullptr); off += align256(cmax * sizeof(float));
-        w.shift[i] = (float*)(base ? base + off : nullptr); off += align256(cmax * sizeof(float));
+        w.scale[i] = (float*)(base ? base + off : nullptr); off += align256(CMAX * b * sizeof(float));
+        w.shift[i] = (float*)(base ? base + off : nullptr); off += align256(CMAX * b * sizeof(float));
     }
     w.stats = (double*)(base ? base + off : nullptr);
-    off += align256((size_t)N_BN * MVS_BN_SLOTS_MAX * 2 * cmax * sizeof(double));
+    off += align256(stats_doubles(b) * sizeof(double));
     w.bytes = off;
     return w;
 }
@@ -261,47 +149,238 @@ RegnetWs carve(char* base, int D, int H, int W, int cin, int b) {
 
 extern "C" size_t mvs_regnet_workspace_bytes(int D, int H, int W, int cin, int base) {
     if (D <= 0 || H <= 0 || W <= 0 || cin <= 0 || base <= 0) return 0;
-    return carve(nullptr, D, H, W, cin, base).bytes;
+    return carve(nullptr, D, H, W, base).bytes;
 }
-
-namespace {
-// layer table (order of the weights array) and offsets of the pre-laid-out weights
-struct PrepLayout { int kind[11]; int ci[11]; int co[11]; size_t off[11]; bool ok[11]; bool bf[11]; size_t total; };
-PrepLayout prep_layout(int cin, int b) {
-    PrepLayout L;
-    const int kind[11] = {1, 1, 1, 0, 0, 0, 0, 2, 2, 2, 0};
-    const int ci[11] = {cin, 2 * b, 4 * b, cin, 2 * b, 4 * b, 8 * b, 8 * b, 4 * b, 2 * b, b};
-    const int co[11] = {2 * b, 4 * b, 8 * b, b, 2 * b, 4 * b, 8 * b, 4 * b, 2 * b, b, 1};
-    size_t off = 0;
-    for (int i = 0; i < 11; ++i) {
-        L.kind[i] = kind[i]; L.ci[i] = ci[i]; L.co[i] = co[i]; L.off[i] = off;
-        L.ok[i] = (i != L62) && (ci[i] % 4 == 0) && conv_coutg(kind[i], ci[i], co[i]) != 0;
-        L.bf[i] = L.ok[i] && kind[i] == 0 && mvs_conv3d_bf16x3_supported(ci[i], co[i]);
-        off += (size_t)27 * ci[i] * co[i];
-    }
-    L.total = off;
-    return L;
-}
-}  // namespace
 
 extern "C" size_t mvs_regnet_prepared_floats(int cin, int base) {
     if (cin <= 0 || base <= 0) return 0;
-    return 2 * prep_layout(cin, base).total;      // fp32 layouts, then bf16 hi|lo layouts
+    return 2 * net_of(cin, base).wtotal;      // fp32 layouts, then bf16 hi|lo layouts
 }
 
 extern "C" int mvs_regnet_prepare_f32(const float* const* weights, int cin, int base, float* prepared,
                                       void* stream) {
     MVS_CHECK_ARG(weights && prepared && cin > 0 && base > 0);
-    PrepLayout L = prep_layout(cin, base);
-    for (int i = 0; i < 11; ++i) {
-        if (!L.ok[i]) continue;
-        int rc = mvs_conv_weight_layout(weights[i], L.kind[i], L.ci[i], L.co[i], prepared + L.off[i], mvs_stream(stream));
+    const Net n = net_of(cin, base);
+    for (int i = 0; i < N_LAYERS; ++i) {
+        if (!n.ok[i]) continue;
+        int rc = mvs_conv_weight_layout(weights[i], NET[i].kind, n.ci[i], n.co[i], prepared + n.woff[i], mvs_stream(stream));
         if (rc) return rc;
-        if (L.bf[i]) {
-            rc = mvs_conv_weight_split(weights[i], L.ci[i], L.co[i],
-                                       reinterpret_cast<unsigned short*>(prepared + L.total + L.off[i]), mvs_stream(stream));
+        if (n.bf[i]) {
+            rc = mvs_conv_weight_split(weights[i], n.ci[i], n.co[i],
+                                       reinterpret_cast<unsigned short*>(prepared + n.wtotal + n.woff[i]), mvs_stream(stream));
             if (rc) return rc;
         }
+    }
+    return 0;
+}
+
+namespace {
+
+// (nslot, n) partial rows of BatchNorm sums -> row 0 holds the total, the other rows zero
+__global__ void bn_fold_rows_kernel(double* stats, int nslot, int n) {
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        double t = stats[j];
+        for (int r = 1; r < nslot; ++r) { t += stats[(size_t)r * n + j]; stats[(size_t)r * n + j] = 0.0; }
+        stats[j] = t;
+    }
+}
+
+// partial rows per layer: only where EVERY layer has an MFMA kernel (the scalar fallback finalises one row)
+// MVS_BN_SLOTS = 1 / 2 / 4 / 8 measured 858 / 864 / 860 / 848 depth maps/s at the metric workload: more rows shorten the
+// producers' atomic tails but every consumer thread adds the rows up again
+constexpr int BN_SLOTS = 2;
+// the fused pass over the cost volume spreads its sums over partial rows too (conv3d_c8.hip, FuseArgs)
+// rows of the fused pair's sums: MVS_PAIR_SLOTS = 8 (round 1) / 4 / 2 / 1 measured 864 / 869 / 869 / 870 depth maps/s -- the
+// consumers (3dconv1_1, 2_0 and the 3 840-workgroup 3dconv6_2) pay for every row they add up
+constexpr int PAIR_SLOTS = 2;
+static_assert(BN_SLOTS <= MVS_BN_SLOTS_MAX && PAIR_SLOTS <= MVS_BN_SLOTS_MAX, "rows beyond the workspace's slab");
+
+// One call of the regulariser: what the steps below share.
+struct Run {
+    const float* cost; int batch, D, H, W, b;
+    const float* const* weights; const float* prepared; const float* const* gammas; const float* const* betas;
+    float eps; float* reg; hipStream_t hs;
+    int impl;
+    Net net;
+    RegnetWs ws;
+    size_t ws_floats1;           // a sample's workspace region (regions are 256-byte aligned)
+    bool all_mfma;
+    int SL;                      // partial rows of every layer's sums
+    int lp;                      // per-layer event slot of this call (mvs_profile_layers), or -1
+    bool pair_done = false;
+    bool finalised[N_BN] = {};
+
+    double* st(int i) const { return ws.stats + (size_t)i * MVS_BN_SLOTS_MAX * 2 * CMAX * b; }
+    int nslot_of(int i) const { return (pair_done && (i == L01 || i == L10)) ? PAIR_SLOTS : SL; }
+    BnSrc bn_of(int i) const {   // producer i's raw BatchNorm sums (i < 0: raw input, no BN)
+        if (i < 0) return BnSrc{nullptr, nullptr, nullptr, 1.0, eps, 0, 1};
+        return BnSrc{st(i), gammas[i], betas[i], count(i), eps, net.co[i], nslot_of(i)};
+    }
+    double count(int i) const { return ((double)batch * D * H * W) / (double)(1 << (3 * out_level(i))); }   // voxels behind a statistic
+    const float* wprep(int i) const { return (prepared && net.ok[i]) ? prepared + net.woff[i] : nullptr; }
+    int mark(int l, int k, hipStream_t s) const { return mvs_prof_layers.mark(lp, 2 * l + k, s); }
+};
+
+// layer `out` of sample bi as its MFMA launcher takes it: in = BN+ReLU(p1) [+ BN+ReLU(p2)] from the producers' raw sums
+ConvArgs layer_args(const Run& r, int bi, int out) {
+    const LayerRow& row = NET[out];
+    const size_t wo = (size_t)bi * r.ws_floats1;
+    const size_t v0 = (size_t)r.D * r.H * r.W;
+    ConvArgs a = conv_args(row.p1 >= 0 ? r.ws.y[row.p1] + wo : r.cost + (size_t)bi * v0 * r.net.ci[out], r.weights[out],
+                           out == L62 ? r.reg + (size_t)bi * v0 : r.ws.y[out] + wo, out == L62 ? nullptr : r.st(out),
+                           r.D >> row.level, r.H >> row.level, r.W >> row.level, r.net.co[out]);
+    a.x2 = row.p2 >= 0 ? r.ws.y[row.p2] + wo : nullptr;
+    a.bn = r.bn_of(row.p1); a.bn2 = r.bn_of(row.p2);
+    a.wprep = r.wprep(out);
+    // opt-in split-precision path: bf16 hi|lo weights live behind the fp32 layouts
+    // (the opt-in split-precision mode keeps every fused / filled fp32 launch of the default mode and uses its bf16 kernel for the one
+    //  layer where it is faster, 3dconv0_1: 32 -> 8 over the whole volume -- round 5; before, it ran all eleven layers apart)
+    if (r.prepared && r.impl == MVS_CONV_IMPL_BF16X3 && r.net.bf[out] && (!r.all_mfma || out == L01))
+        a.wprep_bf = reinterpret_cast<const unsigned short*>(r.prepared + r.net.wtotal + r.net.woff[out]);
+    a.stats_slots = r.SL;
+    return a;
+}
+
+int ensure_final(Run& r, int i) {        // (scale, shift) of producer i for the scalar kernels, once per producer and call
+    if (i < 0 || r.finalised[i]) return 0;
+    r.finalised[i] = true;
+    // the producer may have spread its sums over partial rows: fold them into row 0 (the other rows become zero, so an MFMA
+    // consumer that adds the rows up again still gets the total)
+    if (r.nslot_of(i) > 1) {
+        bn_fold_rows_kernel<<<1, 256, 0, r.hs>>>(r.st(i), r.nslot_of(i), 2 * r.net.co[i]);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return mvs_bn_finalize_f32(r.st(i), r.net.co[i], r.count(i), r.gammas[i], r.betas[i], r.eps, r.ws.scale[i], r.ws.shift[i], r.hs);
+}
+
+int layer_one(Run& r, int bi, int out, hipStream_t s) {
+    const LayerRow& row = NET[out];
+    ConvArgs a = layer_args(r, bi, out);
+    const int ci = r.net.ci[out], co = r.net.co[out];
+    if (r.impl != MVS_CONV_IMPL_SCALAR) {
+        int rc = row.kind == UP ? mvs_deconv3d_mfma_launch(a, ci, co, s) : mvs_conv3d_dispatch(a, ci, co, row.kind == S2 ? 2 : 1, s);
+        // a (D, H, W) outside a layer's MFMA tiling falls back to the shape-generic kernel for THAT layer (AUTO only)
+        if (rc != MVS_E_SHAPE || r.impl != MVS_CONV_IMPL_AUTO) return rc;
+    }
+    int rc;
+    if ((rc = ensure_final(r, row.p1)) || (rc = ensure_final(r, row.p2))) return rc;
+    const float* s1 = row.p1 >= 0 ? r.ws.scale[row.p1] : nullptr; const float* t1 = row.p1 >= 0 ? r.ws.shift[row.p1] : nullptr;
+    const float* s2 = row.p2 >= 0 ? r.ws.scale[row.p2] : nullptr; const float* t2 = row.p2 >= 0 ? r.ws.shift[row.p2] : nullptr;
+    return row.kind == UP ? mvs_deconv3d_scalar(a.x, s1, t1, a.x2, s2, t2, a.w, a.D, a.H, a.W, ci, co, a.y, a.stats, s)
+                          : mvs_conv3d_scalar(a.x, s1, t1, a.x2, s2, t2, a.w, a.D, a.H, a.W, ci, co, row.kind == S2 ? 2 : 1, a.y, a.stats, s);
+}
+
+// a plain layer on stream s: for all samples of the batch before any consumer is launched
+int layer(Run& r, int out, hipStream_t s) {
+    int rc = r.mark(out, 0, s);
+    for (int bi = 0; bi < r.batch && !rc; ++bi) rc = layer_one(r, bi, out, s);
+    return rc ? rc : r.mark(out, 1, s);
+}
+
+// ---- fused forms.  Each answers APART when it does not apply -- its precondition fails, or its first launch answers
+// MVS_E_SHAPE -- and or_apart() then runs its layers one by one; any other code is the call's. ----------------------------
+constexpr int APART = -1000;      // no MVS_E_* code and no hipError_t
+
+int or_apart(Run& r, int rc, std::initializer_list<int> layers) {
+    if (rc != APART) return rc;
+    for (int l : layers) if ((rc = layer(r, l, r.hs))) return rc;
+    return 0;
+}
+
+// 3dconv1_0 and 3dconv0_1 read the same volume, the raw cost volume: one fused pass when the shape is the one conv3d_c8.hip is
+// built for.  (Its launcher answers MVS_E_SHAPE for volumes of 2 GB and more, so a pair that ran implies all_mfma.)
+// Reports under 3dconv0_1; the dominant-kernel profiler (mvs_profile_dominant) brackets it and counts it once its end is recorded.
+int fused_pair(Run& r) {
+    if (!((r.impl == MVS_CONV_IMPL_AUTO || r.impl == MVS_CONV_IMPL_MFMA) && r.net.ci[L01] == 32 && r.b == 8)) return APART;
+    const int slot = mvs_prof_dominant.claim();
+    int rc;
+    if ((rc = mvs_prof_dominant.mark(slot, 0, r.hs)) || (rc = r.mark(L01, 0, r.hs))) return rc;
+    for (int bi = 0; bi < r.batch; ++bi) {
+        const size_t wo = (size_t)bi * r.ws_floats1;
+        ConvArgs a = conv_args(r.cost + (size_t)bi * r.D * r.H * r.W * r.net.ci[L01], r.weights[L01], r.ws.y[L01] + wo, r.st(L01),
+                               r.D, r.H, r.W, r.net.co[L01]);
+        a.wprep = r.wprep(L01);
+        rc = mvs_conv3d_c8_s2_launch(a, r.weights[L10], r.ws.y[L10] + wo, r.st(L10), r.hs, PAIR_SLOTS, PAIR_SLOTS);
+        if (rc) return rc == MVS_E_SHAPE ? APART : rc;
+    }
+    if ((rc = r.mark(L01, 1, r.hs)) || (rc = mvs_prof_dominant.mark(slot, 1, r.hs))) return rc;
+    mvs_prof_dominant.commit(slot);
+    r.pair_done = true;
+    return 0;
+}
+
+// 3dconv1_1 (stride 1) and 3dconv2_0 (stride 2) read the same tensor, BN + ReLU of 3dconv1_0: one fused pass when the
+// shape is the one conv3d_mfma.hip builds it for (round 4), as for the two consumers of the cost volume above.
+// Reports under 3dconv1_1.
+int fuse2(Run& r) {
+    const int D1 = r.D >> 1, H1 = r.H >> 1, W1 = r.W >> 1;
+    if (!r.all_mfma || (D1 & 1) || (H1 & 1) || (W1 & 1)) return APART;
+    int rc = r.mark(L11, 0, r.hs);
+    for (int bi = 0; bi < r.batch && !rc; ++bi) {
+        const size_t wo = (size_t)bi * r.ws_floats1;
+        ConvArgs a = conv_args(r.ws.y[L10] + wo, r.weights[L11], r.ws.y[L11] + wo, r.st(L11), D1, H1, W1, r.net.co[L11]);
+        a.bn = r.bn_of(L10); a.wprep = r.wprep(L11); a.stats_slots = r.SL;
+        rc = mvs_conv3d_s1_fuse2_launch(a, r.weights[L20], r.ws.y[L20] + wo, r.st(L20), r.hs);
+    }
+    if (rc) return rc == MVS_E_SHAPE ? APART : rc;
+    return r.mark(L11, 1, r.hs);
+}
+
+// Round 6 experiment (MVS_HOOK_REGNET_SIDE_BRANCH): 3dconv1_1 is only read by 3dconv6_0, three launches of the latency-bound
+// low-resolution chain later -- on a side stream of the caller's stream set (mvs_gru_prepare) it runs BESIDE 3dconv2_0 and the
+// chain instead of in front of them; 3dconv2_0 then runs apart from it.  MEASURED: 986.5-987.8 against 982.4-983.7 depth maps/s
+// (+0.4 %, profiles/r06_regnet_side_branch.txt) -- the chain's launches stretch by nearly what the branch hides, as in round 1.
+// (Round 1 ran the same-resolution branches on a side stream beside the encoder's tail; with the block kernels of conv3d_os.hip a
+// layer running beside the chain slows it by more than it hides -- 826 depth maps/s with the fork, 837 without -- so the product
+// is one stream.)  Stays a measurement hook.  The caller's stream joins the side stream on every exit after the fork.
+struct SideBranch {
+    hipStream_t hs = nullptr, side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    enum { NONE, FORKED, BRANCH_RECORDED } state = NONE;
+    int fork() {
+        hipError_t e = hipEventRecord(ev_fork, hs);
+        if (e == hipSuccess) e = hipStreamWaitEvent(side, ev_fork, 0);
+        if (e == hipSuccess) state = FORKED;
+        return (int)e;
+    }
+    int branch_end() {
+        const hipError_t e = hipEventRecord(ev_join, side);
+        if (e == hipSuccess) state = BRANCH_RECORDED;
+        return (int)e;
+    }
+    int join() {      // no-op when no branch is open
+        if (state == NONE) return 0;
+        hipError_t e = state == FORKED ? hipEventRecord(ev_join, side) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamWaitEvent(hs, ev_join, 0);
+        state = NONE;
+        return (int)e;
+    }
+    ~SideBranch() { join(); }
+};
+int side_branch(Run& r, SideBranch& sb) {
+    int rc;
+    if ((rc = sb.fork()) || (rc = layer(r, L11, sb.side)) || (rc = sb.branch_end())) return rc;
+    return layer(r, L20, r.hs);
+}
+
+// 3dconv2_1 (only the decoder's 3dconv5_0 reads it) rides as filler blocks in the launches of the 1/8-resolution chain
+// 3dconv3_0 -> 3_1 -> 4_0 (conv3d_os.hip, conv3d_os_filled_kernel; round 4) when every layer has its block kernel: needs
+// prepared weights.  A filled launch reports under its chain layer.  MVS_E_SHAPE from the second or third launch is an error.
+int filled_chain(Run& r) {
+    if (!(r.all_mfma && r.prepared && r.net.ok[L21] && r.net.ok[L30] && r.net.ok[L31] && r.net.ok[L40])) return APART;
+    const int nfill = mvs_conv3d_os_filler_blocks(r.D >> 2, r.H >> 2, r.W >> 2);
+    // share of 3dconv2_1's blocks per chain launch, in 1/1000 (multiples of 8 blocks: one per XCD)
+    const int f0 = (nfill * FILL_3_0 / 1000) & ~7, f1 = (nfill * FILL_3_1 / 1000) & ~7;
+    const int chain[3] = {L30, L31, L40}, first[3] = {0, f0, f0 + f1}, count[3] = {f0, f1, nfill - f0 - f1};
+    for (int k = 0; k < 3; ++k) {
+        const int out = chain[k];
+        int rc = r.mark(out, 0, r.hs);
+        for (int bi = 0; bi < r.batch && !rc; ++bi)
+            rc = mvs_conv3d_os_filled_launch(layer_args(r, bi, out), NET[out].kind, r.net.ci[out], r.net.co[out],
+                                             layer_args(r, bi, L21), first[k], count[k], r.hs);
+        if (!rc) rc = r.mark(out, 1, r.hs);
+        if (rc) return (rc == MVS_E_SHAPE && k == 0) ? APART : rc;
     }
     return 0;
 }
@@ -309,241 +388,44 @@ extern "C" int mvs_regnet_prepare_f32(const float* const* weights, int cin, int 
 // `batch` samples share every BatchNorm layer's statistics (the reference normalises over (B,D,H,W), network.py:496-506):
 // each layer runs for all samples -- their float64 sums land in the same slab -- before any consumer reads them.
 // cost (B,D,H,W,cin), reg (B,D,H,W), workspace = B consecutive per-sample regions (the sums live in the first).
-static int regnet_run(const float* cost, int batch, int D, int H, int W, int cin, int base,
-                      const float* const* weights, const float* prepared, const float* const* gammas,
-                      const float* const* betas, float eps, void* workspace, size_t workspace_bytes,
-                      float* reg, void* stream, bool stats_zeroed = false) {
-    const PrepLayout lay = prep_layout(cin, base);
+// stats_zeroed: the caller has cleared the sums already (mvs_depth_from_features_f32: in its homography launch).
+int regnet_run(const float* cost, int batch, int D, int H, int W, int cin, int base,
+               const float* const* weights, const float* prepared, const float* const* gammas,
+               const float* const* betas, float eps, void* workspace, size_t workspace_bytes,
+               float* reg, void* stream, bool stats_zeroed = false) {
     MVS_CHECK_ARG(cost && weights && gammas && betas && workspace && reg);
     MVS_CHECK_ARG(batch > 0 && D > 0 && H > 0 && W > 0 && cin > 0 && base > 0);
     if ((D % 8) || (H % 8) || (W % 8)) return MVS_E_SHAPE;
-    const size_t ws_bytes1 = carve(nullptr, D, H, W, cin, base).bytes;
-    if (workspace_bytes < ws_bytes1 * (size_t)batch) return MVS_E_WORKSPACE;
-    RegnetWs ws = carve((char*)workspace, D, H, W, cin, base);
-    const size_t ws_floats1 = ws_bytes1 / sizeof(float);        // regions are 256-byte aligned
-    const size_t cost1 = (size_t)D * H * W * cin, reg1 = (size_t)D * H * W;
-    const int b = base, cmax = 8 * b;
-    const int D1 = D / 2, H1 = H / 2, W1 = W / 2, D2 = D / 4, H2 = H / 4, W2 = W / 4,
-              D3 = D / 8, H3 = H / 8, W3 = W / 8;
-    const double v0 = (double)batch * D * H * W, v1 = v0 / 8, v2 = v1 / 8, v3 = v2 / 8;     // voxels behind each statistic
+    const RegnetWs ws = carve((char*)workspace, D, H, W, base);
+    if (workspace_bytes < ws.bytes * (size_t)batch) return MVS_E_WORKSPACE;
     int rc;
-    if (!stats_zeroed && (rc = mvs_zero_f64(ws.stats, (size_t)N_BN * MVS_BN_SLOTS_MAX * 2 * cmax, stream))) return rc;
-    hipStream_t hs = mvs_stream(stream);
-    int lp = -1;                                     // per-layer event slot of this call (mvs_profile_layers)
-    if (g_lprof.on && g_lprof.used < 32) {
-        lp = g_lprof.used;
-        if (lp >= g_lprof.created) {
-            for (int l = 0; l < 11 && lp >= 0; ++l)
-                for (int k = 0; k < 2 && lp >= 0; ++k)
-                    if (hipEventCreate(&g_lprof.ev[lp][l][k]) != hipSuccess) lp = -1;
-            if (lp >= 0) g_lprof.created = lp + 1;
-        }
-        if (lp >= 0) { for (int l = 0; l < 11; ++l) g_lprof.hit[lp][l] = false; g_lprof.used = lp + 1; }
-    }
-    auto lp_mark = [&](int l, int k, hipStream_t s_) -> int {
-        if (lp < 0) return 0;
-        hipError_t e = hipEventRecord(g_lprof.ev[lp][l][k], s_);
-        if (e == hipSuccess && k == 1) g_lprof.hit[lp][l] = true;
-        return (int)e;
-    };
-    const int ch[N_BN] = {2 * b, 4 * b, 8 * b, b, 2 * b, 4 * b, 8 * b, 4 * b, 2 * b, b};
-    const double cnt[N_BN] = {v1, v2, v3, v0, v1, v2, v3, v2, v1, v0};
-    auto st = [&](int i) { return ws.stats + (size_t)i * MVS_BN_SLOTS_MAX * 2 * cmax; };
-    // partial rows per layer: only where EVERY layer has an MFMA kernel (the scalar fallback finalises one row)
-    // MVS_BN_SLOTS = 1 / 2 / 4 / 8 measured 858 / 864 / 860 / 848 depth maps/s at the metric workload: more rows shorten the
-    // producers' atomic tails but every consumer thread adds the rows up again
-    constexpr int slots_env = 2;
+    if (!stats_zeroed && (rc = mvs_zero_f64(ws.stats, stats_doubles(base), stream))) return rc;
+    const int impl = mvs_get_conv_impl();
+    // 2 rows per layer only where every layer has its MFMA kernel
     // (volumes of 2 GB and more leave the 32-bit-offset MFMA kernels for the generic ones: one row there)
-    // (the opt-in split-precision mode keeps every fused / filled fp32 launch of the default mode and uses its bf16 kernel for the one
-    //  layer where it is faster, 3dconv0_1: 32 -> 8 over the whole volume -- round 5; before, it ran all eleven layers apart)
-    const bool all_mfma = (g_conv_impl == MVS_CONV_IMPL_AUTO || g_conv_impl == MVS_CONV_IMPL_MFMA || g_conv_impl == MVS_CONV_IMPL_BF16X3) &&
-                          cin == 32 && b == 8 && (long long)D * H * W * cin * 4 < (1LL << 31);
-    const int SL = all_mfma ? (slots_env < 1 ? 1 : slots_env > MVS_BN_SLOTS_MAX ? MVS_BN_SLOTS_MAX : slots_env) : 1;
-    bool finalised[N_BN] = {false};
-    bool pair_done = false;
-    // the fused pass over the cost volume spreads its sums over partial rows (conv3d_c8.hip, FuseArgs): as many as
-    // fit the layer's 2*cmax-double slab
-    // rows of the fused pair's sums: MVS_PAIR_SLOTS = 8 (round 1) / 4 / 2 / 1 measured 864 / 869 / 869 / 870 depth maps/s -- the
-    // consumers (3dconv1_1, 2_0 and the 3 840-workgroup 3dconv6_2) pay for every row they add up
-    constexpr int pair_slots = 2;
-    const int slots01 = all_mfma ? pair_slots : ((2 * cmax) / (2 * b) < 8 ? (2 * cmax) / (2 * b) : 8);
-    const int slots10 = all_mfma ? pair_slots : ((2 * cmax) / (4 * b) < 8 ? (2 * cmax) / (4 * b) : 8);
-    auto bn_of = [&](int i) {      // producer i's raw BatchNorm sums (i < 0: raw input, no BN)
-        BnSrc s{nullptr, nullptr, nullptr, 1.0, eps, 0, 1};
-        if (i >= 0) s = BnSrc{st(i), gammas[i], betas[i], cnt[i], eps, ch[i],
-                              (pair_done && i == L01) ? slots01 : (pair_done && i == L10) ? slots10 : SL};      // = nslot_of(i)
-        return s;
-    };
-    auto nslot_of = [&](int i) { return (pair_done && i == L01) ? slots01 : (pair_done && i == L10) ? slots10 : SL; };
-    auto ensure_final = [&](int i) -> int {        // (scale, shift) of producer i for the scalar kernels
-        if (i < 0 || finalised[i]) return 0;
-        finalised[i] = true;
-        // the producer may have spread its sums over partial rows: fold them into row 0 (the other rows become zero, so an MFMA
-        // consumer that adds the rows up again still gets the total)
-        if (nslot_of(i) > 1) {
-            bn_fold_rows_kernel<<<1, 256, 0, mvs_stream(stream)>>>(st(i), nslot_of(i), 2 * ch[i]);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return (int)e;
-        }
-        return mvs_bn_finalize_f32(st(i), ch[i], cnt[i], gammas[i], betas[i], eps, ws.scale[i], ws.shift[i], stream);
-    };
-    // one layer: in = BN+ReLU(producer p1) [+ BN+ReLU(producer p2)], out = layer `out` (or reg)
-    auto layer_one = [&](int bi, bool deconv, int p1, int p2, int out, int d, int h, int w, int ci, int co,
-                         int stride, hipStream_t hs) -> int {
-        const size_t wo = (size_t)bi * ws_floats1;                  // this sample's workspace region
-        const float* x = p1 >= 0 ? ws.y[p1] + wo : cost + (size_t)bi * cost1;
-        const float* x2 = p2 >= 0 ? ws.y[p2] + wo : nullptr;
-        float* y = out == L62 ? reg + (size_t)bi * reg1 : ws.y[out] + wo;
-        double* so = out == L62 ? nullptr : st(out);
-        if (g_conv_impl != MVS_CONV_IMPL_SCALAR) {
-            const float* wp = (prepared && lay.ok[out]) ? prepared + lay.off[out] : nullptr;
-            // opt-in split-precision path: bf16 hi|lo weights live behind the fp32 layouts
-            const unsigned short* wbf = (prepared && g_conv_impl == MVS_CONV_IMPL_BF16X3 && lay.bf[out] && (!all_mfma || out == L01))
-                ? reinterpret_cast<const unsigned short*>(prepared + lay.total + lay.off[out]) : nullptr;
-            int r = deconv ? mvs_deconv3d_mfma_bn(x, bn_of(p1), x2, bn_of(p2), weights[out], wp, d, h, w, ci, co, y, so, hs, SL)
-                           : mvs_conv3d_mfma_bn(x, bn_of(p1), x2, bn_of(p2), weights[out], wp, wbf, d, h, w, ci, co, stride, y, so, hs, SL);
-            // a (D, H, W) outside a layer's MFMA tiling falls back to the shape-generic kernel for THAT layer (AUTO only)
-            if (r != MVS_E_SHAPE || g_conv_impl == MVS_CONV_IMPL_MFMA || g_conv_impl == MVS_CONV_IMPL_BF16X3) return r;
-        }
-        int r;
-        if ((r = ensure_final(p1)) || (r = ensure_final(p2))) return r;
-        const float* s1 = p1 >= 0 ? ws.scale[p1] : nullptr; const float* t1 = p1 >= 0 ? ws.shift[p1] : nullptr;
-        const float* s2 = p2 >= 0 ? ws.scale[p2] : nullptr; const float* t2 = p2 >= 0 ? ws.shift[p2] : nullptr;
-        return deconv ? mvs_deconv3d_scalar(x, s1, t1, x2, s2, t2, weights[out], d, h, w, ci, co, y, so, hs)
-                      : mvs_conv3d_scalar(x, s1, t1, x2, s2, t2, weights[out], d, h, w, ci, co, stride, y, so, hs);
-    };
-    auto layer_run = [&](bool deconv, int p1, int p2, int out, int d, int h, int w, int ci, int co,
-                         int stride, hipStream_t hs) -> int {
-        for (int bi = 0; bi < batch; ++bi) {
-            int r = layer_one(bi, deconv, p1, p2, out, d, h, w, ci, co, stride, hs);
-            if (r) return r;
-        }
-        return 0;
-    };
-    auto layer = [&](bool deconv, int p1, int p2, int out, int d, int h, int w, int ci, int co,
-                     int stride, hipStream_t hs_) -> int {
-        int r = lp_mark(out, 0, hs_);
-        if (!r) r = layer_run(deconv, p1, p2, out, d, h, w, ci, co, stride, hs_);
-        if (!r) r = lp_mark(out, 1, hs_);
-        return r;
-    };
-#define RUN(call) do { if ((rc = (call))) return rc; } while (0)
-#define HIP_RUN(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return (int)e__; } while (0)
-    // encoder on the raw cost volume (mvsnetworks.py:130-136).  3dconv1_0 and 3dconv0_1 read the same
-    // volume: one fused pass when the shape is the one conv3d_c8.hip is built for.
-    if ((g_conv_impl == MVS_CONV_IMPL_AUTO || g_conv_impl == MVS_CONV_IMPL_MFMA) && cin == 32 && b == 8) {
-        auto pair_args = [&](int bi) {
-            return ConvArgs{cost + (size_t)bi * cost1, nullptr, nullptr, nullptr, nullptr, nullptr, weights[L01],
-                            ws.y[L01] + (size_t)bi * ws_floats1, st(L01), D, H, W, b,
-                            0, 0, 0, 0, {}, {}, prepared ? prepared + lay.off[L01] : nullptr, nullptr};
-        };
-        int slot = -1;
-        if (g_prof.on && g_prof.used < 64) {
-            slot = g_prof.used;
-            if (slot >= g_prof.created) {
-                if (hipEventCreate(&g_prof.ev[slot][0]) != hipSuccess || hipEventCreate(&g_prof.ev[slot][1]) != hipSuccess) slot = -1;
-                else g_prof.created = slot + 1;
-            }
-        }
-        if (slot >= 0) HIP_RUN(hipEventRecord(g_prof.ev[slot][0], hs));
-        RUN(lp_mark(L01, 0, hs));
-        for (int bi = 0; bi < batch; ++bi) {
-            rc = mvs_conv3d_c8_s2_launch(pair_args(bi), weights[L10], ws.y[L10] + (size_t)bi * ws_floats1, st(L10), hs, slots01, slots10);
-            if (rc) break;
-        }
-        if (rc == 0) RUN(lp_mark(L01, 1, hs));
-        if (slot >= 0 && rc == 0) { HIP_RUN(hipEventRecord(g_prof.ev[slot][1], hs)); g_prof.used = slot + 1; }
-        if (rc == 0) pair_done = true;
-        else if (rc != MVS_E_SHAPE) return rc;
+    const bool all_mfma = impl != MVS_CONV_IMPL_SCALAR && cin == 32 && base == 8 && (long long)D * H * W * cin * 4 < (1LL << 31);
+    Run r{cost, batch, D, H, W, base, weights, prepared, gammas, betas, eps, reg, mvs_stream(stream), impl,
+          net_of(cin, base), ws, ws.bytes / sizeof(float), all_mfma, all_mfma ? BN_SLOTS : 1, mvs_prof_layers.claim()};
+    mvs_prof_layers.commit(r.lp);
+
+    SideBranch sb;
+    bool side = false;
+    if (mvs_hook(MVS_HOOK_REGNET_SIDE_BRANCH) && all_mfma && batch == 1 && r.lp < 0) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const bool capturing = hipStreamIsCapturing(r.hs, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+        sb.hs = r.hs;
+        side = !capturing && mvs_stream_set_side(r.hs, &sb.side, &sb.ev_fork, &sb.ev_join);
     }
-    if (!pair_done) {
-        RUN(layer(false, -1, -1, L10, D, H, W, cin, 2 * b, 2, hs));
-        RUN(layer(false, -1, -1, L01, D, H, W, cin, b, 1, hs));
-    }
-    // The same-resolution branches 3dconv1_1 / 3dconv2_1 (mvsnetworks.py:138-141) are only needed by the decoder.  (Round 1 ran
-    // them on a side stream beside the encoder's tail; with the block kernels of conv3d_os.hip a layer running beside the
-    // chain slows it by more than it hides -- 826 depth maps/s with the fork, 837 without -- so everything is one stream.)
-    // 3dconv1_1 (stride 1) and 3dconv2_0 (stride 2) read the same tensor, BN + ReLU of 3dconv1_0: one fused pass when the
-    // shape is the one conv3d_mfma.hip builds it for (round 4), as for the two consumers of the cost volume above.
-    bool pair2_done = false;
-    // Round 6 experiment (MVS_HOOK_REGNET_SIDE_BRANCH): 3dconv1_1 is only read by 3dconv6_0, three launches of the latency-bound
-    // low-resolution chain later -- on a side stream of the caller's stream set (mvs_gru_prepare) it runs BESIDE 3dconv2_0 and the
-    // chain instead of in front of them; 3dconv2_0 then runs apart from it.  MEASURED: 986.5-987.8 against 982.4-983.7 depth maps/s
-    // (+0.4 %, profiles/r06_regnet_side_branch.txt) -- the chain's launches stretch by nearly what the branch hides, as in round 1.
-    // Stays a measurement hook (an error return between fork and join would leave the side stream un-joined).
-    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool side_branch = false;
-    {
-        hipStreamCaptureStatus cs_ = hipStreamCaptureStatusNone;
-        const bool capturing_ = hipStreamIsCapturing(hs, &cs_) == hipSuccess && cs_ != hipStreamCaptureStatusNone;
-        if (mvs_hook(MVS_HOOK_REGNET_SIDE_BRANCH) && all_mfma && batch == 1 && !capturing_ && lp < 0)
-            side_branch = mvs_stream_set_side(hs, &side, &ev_fork, &ev_join);
-    }
-    if (side_branch) {
-        HIP_RUN(hipEventRecord(ev_fork, hs));
-        HIP_RUN(hipStreamWaitEvent(side, ev_fork, 0));
-        RUN(layer(false, L10, -1, L11, D1, H1, W1, 2 * b, 2 * b, 1, side));
-        HIP_RUN(hipEventRecord(ev_join, side));
-        RUN(layer(false, L10, -1, L20, D1, H1, W1, 2 * b, 4 * b, 2, hs));
-        pair2_done = true;
-    }
-    if (!pair2_done && all_mfma && !(D1 & 1) && !(H1 & 1) && !(W1 & 1)) {
-        RUN(lp_mark(L11, 0, hs));
-        for (int bi = 0; bi < batch; ++bi) {
-            const size_t wo = (size_t)bi * ws_floats1;
-            rc = mvs_conv3d_s1s2_16_bn(ws.y[L10] + wo, bn_of(L10), weights[L11], prepared ? prepared + lay.off[L11] : nullptr,
-                                       D1, H1, W1, ws.y[L11] + wo, st(L11), weights[L20], ws.y[L20] + wo, st(L20), hs, SL);
-            if (rc) break;
-        }
-        if (rc == 0) { RUN(lp_mark(L11, 1, hs)); pair2_done = true; }
-        else if (rc != MVS_E_SHAPE) return rc;
-    }
-    if (!pair2_done) {
-        RUN(layer(false, L10, -1, L11, D1, H1, W1, 2 * b, 2 * b, 1, hs));
-        RUN(layer(false, L10, -1, L20, D1, H1, W1, 2 * b, 4 * b, 2, hs));
-    }
-    // 3dconv2_1 (only the decoder's 3dconv5_0 reads it) rides as filler blocks in the launches of the 1/8-resolution chain
-    // 3dconv3_0 -> 3_1 -> 4_0 (conv3d_os.hip, conv3d_os_filled_kernel; round 4) when every layer has its block kernel.
-    bool filled = false;
-    if (all_mfma && prepared && lay.ok[L21] && lay.ok[L30] && lay.ok[L31] && lay.ok[L40]) {
-        const int nfill = mvs_conv3d_os_filler_blocks(D2, H2, W2);
-        // share of 3dconv2_1's blocks per chain launch, in 1/1000 (multiples of 8 blocks: one per XCD)
-        const int f0 = (nfill * FILL_3_0 / 1000) & ~7, f1 = (nfill * FILL_3_1 / 1000) & ~7;
-        const int first[3] = {0, f0, f0 + f1}, count[3] = {f0, f1, nfill - f0 - f1};
-        const int outs[3] = {L30, L31, L40}, prods[3] = {L20, L30, L31}, kinds[3] = {1, 0, 2};
-        const int dd[3] = {D2, D3, D3}, hh[3] = {H2, H3, H3}, ww[3] = {W2, W3, W3};
-        auto os_args = [&](int bi, int p1, int out, int d, int h, int w) {
-            const size_t wo = (size_t)bi * ws_floats1;
-            return ConvArgs{ws.y[p1] + wo, nullptr, nullptr, nullptr, nullptr, nullptr, weights[out], ws.y[out] + wo, st(out),
-                            d, h, w, lay.co[out], 0, 0, 0, 0, bn_of(p1), bn_of(-1), prepared + lay.off[out], nullptr, SL};
-        };
-        rc = 0;
-        for (int k = 0; k < 3 && rc == 0; ++k) {
-            RUN(lp_mark(outs[k], 0, hs));
-            for (int bi = 0; bi < batch && rc == 0; ++bi)
-                rc = mvs_conv3d_os_filled_launch(os_args(bi, prods[k], outs[k], dd[k], hh[k], ww[k]), kinds[k], lay.ci[outs[k]],
-                                                 lay.co[outs[k]], os_args(bi, L20, L21, D2, H2, W2), first[k], count[k], hs);
-            if (rc == 0) RUN(lp_mark(outs[k], 1, hs));
-            else if (!(rc == MVS_E_SHAPE && k == 0)) return rc;
-        }
-        filled = rc == 0;
-    }
-    if (!filled) {
-        RUN(layer(false, L20, -1, L21, D2, H2, W2, 4 * b, 4 * b, 1, hs));
-        RUN(layer(false, L20, -1, L30, D2, H2, W2, 4 * b, 8 * b, 2, hs));
-        RUN(layer(false, L30, -1, L31, D3, H3, W3, 8 * b, 8 * b, 1, hs));
-        // decoder with additive skips (mvsnetworks.py:146-157)
-        RUN(layer(true, L31, -1, L40, D3, H3, W3, 8 * b, 4 * b, 2, hs));
-    }
-    RUN(layer(true, L40, L21, L50, D2, H2, W2, 4 * b, 2 * b, 2, hs));
-    if (side_branch) HIP_RUN(hipStreamWaitEvent(hs, ev_join, 0));      // 3dconv6_0 reads 3dconv1_1
-    RUN(layer(true, L50, L11, L60, D1, H1, W1, 2 * b, b, 2, hs));
-    // output conv, no BN / ReLU / bias (mvsnetworks.py:158)
-    RUN(layer(false, L60, L01, L62, D, H, W, b, 1, 1, hs));
-#undef RUN
-#undef HIP_RUN
-    return 0;
+    if ((rc = or_apart(r, fused_pair(r), {L10, L01}))) return rc;
+    if ((rc = or_apart(r, side ? side_branch(r, sb) : fuse2(r), {L11, L20}))) return rc;
+    if ((rc = or_apart(r, filled_chain(r), {L21, L30, L31, L40}))) return rc;
+    if ((rc = layer(r, L50, r.hs))) return rc;
+    if ((rc = sb.join())) return rc;                       // 3dconv6_0 reads 3dconv1_1
+    if ((rc = layer(r, L60, r.hs))) return rc;
+    return layer(r, L62, r.hs);
 }
+
+}  // namespace
 
 extern "C" int mvs_regnet_us0_f32(const float* cost, int D, int H, int W, int cin, int base,
                                   const float* const* weights, const float* const* gammas,
@@ -573,10 +455,6 @@ extern "C" int mvs_regnet_us0_batch_f32(const float* cost, int batch, int D, int
 }
 
 // ---- features -> depth in one call (model.py:374-502 after the towers) ---------------------------------------------
-int mvs_homography_transforms_zero(const float* cams, int view_num, int depth_num, float depth_start,
-                                   float depth_interval, float depth_end, int inverse_depth, float* transforms,
-                                   double* zero, int zero_n, hipStream_t st);
-
 extern "C" int mvs_depth_from_features_f32(const float* features, const float* cams, int view_num, int depth_num,
                                            int H, int W, int C, int base, float depth_start, float depth_interval,
                                            float depth_end, int inverse_depth, int variant,
@@ -587,23 +465,16 @@ extern "C" int mvs_depth_from_features_f32(const float* features, const float* c
     MVS_CHECK_ARG(features && cams && weights && gammas && betas && transforms && cost && workspace && reg && depth && prob);
     MVS_CHECK_ARG(view_num >= 2 && depth_num >= 1 && H > 0 && W > 0 && C > 0 && base > 0);
     if ((depth_num % 8) || (H % 8) || (W % 8)) return MVS_E_SHAPE;
-    RegnetWs ws = carve((char*)workspace, depth_num, H, W, C, base);
+    RegnetWs ws = carve((char*)workspace, depth_num, H, W, base);
     if (workspace_bytes < ws.bytes) return MVS_E_WORKSPACE;
     int rc;
-    int sp = -1;                                     // stage event slot of this call (mvs_profile_stages)
-    if (g_sprof.on && g_sprof.used < 32) {
-        sp = g_sprof.used;
-        if (sp >= g_sprof.created) {
-            for (int k = 0; k < 4 && sp >= 0; ++k) if (hipEventCreate(&g_sprof.ev[sp][k]) != hipSuccess) sp = -1;
-            if (sp >= 0) g_sprof.created = sp + 1;
-        }
-        if (sp >= 0) g_sprof.used = sp + 1;
-    }
-    auto mark = [&](int k) -> int { return sp < 0 ? 0 : (int)hipEventRecord(g_sprof.ev[sp][k], mvs_stream(stream)); };
+    const int sp = mvs_prof_stages.claim();          // stage event slot of this call (mvs_profile_stages)
+    mvs_prof_stages.commit(sp);
+    auto mark = [&](int k) { return mvs_prof_stages.mark(sp, k, mvs_stream(stream)); };
     if ((rc = mark(0))) return rc;
     // plane homographies -> 8-vectors, and the zero-fill of this depth map's BatchNorm sums, in one launch
     if ((rc = mvs_homography_transforms_zero(cams, view_num, depth_num, depth_start, depth_interval, depth_end, inverse_depth,
-                                             transforms, ws.stats, N_BN * MVS_BN_SLOTS_MAX * 2 * 8 * base, mvs_stream(stream)))) return rc;
+                                             transforms, ws.stats, (int)stats_doubles(base), mvs_stream(stream)))) return rc;
     if ((rc = mvs_cost_volume_f32(features, features + (size_t)H * W * C, transforms, view_num, depth_num, 0, depth_num,
                                   H, W, C, variant, 0, 0, cost, stream))) return rc;
     if ((rc = mark(1))) return rc;

@@ -438,6 +438,64 @@ def test_regnet_filler_launches_equal_the_layers_apart(shape):
         assert rel_l1(n(filled), exp) < 2e-5
 
 
+REGNET_LAYERS = ("1_0", "2_0", "3_0", "0_1", "1_1", "2_1", "3_1", "4_0", "5_0", "6_0", "6_2")      # weight order
+# (entry, conv impl, hooks, (D, H, W), layers WITHOUT a launch of their own).  A fused launch reports under one of its layers
+# (the pair under 0_1, 1_1 + 2_0 under 1_1, a filled launch under its chain layer); the others then report 0.
+REGNET_ROUTES = [
+    ("prepared", "auto", {}, (32, 32, 64), {"1_0", "2_0", "2_1"}),
+    ("prepared", "auto", {}, (40, 24, 48), {"1_0", "2_0", "2_1"}),
+    ("prepared", "auto", {"conv_no_fuse2": 1}, (32, 32, 64), {"1_0", "2_1"}),
+    ("prepared", "auto", {"conv_no_fuse2": 1}, (40, 24, 48), {"1_0", "2_1"}),
+    ("plain", "auto", {}, (32, 32, 64), {"1_0", "2_0"}),
+    ("prepared", "scalar", {}, (8, 16, 16), set()),
+    ("prepared", "bf16x3", {}, (32, 32, 64), {"2_0", "2_1"}),
+    ("prepared", "auto", {}, (8, 8, 8), {"1_0", "2_0", "2_1"}),
+    ("batch", "auto", {}, (32, 32, 64), {"1_0", "2_0", "2_1"}),
+]
+
+
+@pytest.mark.parametrize("entry,impl,hooks,shape,fused_away", REGNET_ROUTES,
+                         ids=["%s-%s-%s-%dx%dx%d" % (e, i, "+".join(h) or "default", *s) for e, i, h, s, _ in REGNET_ROUTES])
+def test_regnet_routes_are_the_recorded_ones(entry, impl, hooks, shape, fused_away):
+    """Every route of the regulariser computes the same numbers, so the parity tests cannot see a layer that went down another
+    route.  This pins the routes: one call under mvs_profile_layers, then WHICH of the eleven layers report a time of their
+    own.  The patterns were recorded from the library before regnet.hip's launch plan became a table and hold after it."""
+    import ctypes as C
+    from mvsnet_amd.model import BN_EPSILON, RegNetWeights, regnet_us0
+    lib = L.load()
+    D, H, W = shape
+    params = S.make_regnet_params("normal", seed=41, random_affine=True)
+    wts = RegNetWeights(params, DEV)
+    batch = 2 if entry == "batch" else 1
+    cost = t(np.abs(np.random.RandomState(42).standard_normal((batch, D, H, W, 32))).astype(np.float32))
+    ms, count = (C.c_double * 11)(), C.c_int(-1)
+    L.set_conv_impl(impl)
+    try:
+        with L.test_hooks(**hooks):
+            L.check(lib.mvs_profile_layers(1), "mvs_profile_layers")
+            try:
+                if entry == "plain":
+                    reg = torch.empty((D, H, W), device=DEV, dtype=torch.float32)
+                    ws = torch.empty(lib.mvs_regnet_workspace_bytes(D, H, W, 32, wts.base), device=DEV, dtype=torch.uint8)
+                    L.check(lib.mvs_regnet_us0_f32(L.ptr(cost), D, H, W, 32, wts.base, wts.w_ptrs, wts.g_ptrs, wts.b_ptrs,
+                                                   BN_EPSILON, C.c_void_p(ws.data_ptr()), ws.numel(), L.ptr(reg),
+                                                   L.stream_ptr()), "mvs_regnet_us0_f32")
+                else:
+                    reg = regnet_us0(cost if entry == "batch" else cost[0], wts)
+                L.check(lib.mvs_profile_layers_ms(ms, C.byref(count)), "mvs_profile_layers_ms")
+            finally:
+                lib.mvs_profile_layers(0)
+    finally:
+        L.set_conv_impl("auto")
+    assert bool(torch.isfinite(reg).all())
+    silent = {name for name, v in zip(REGNET_LAYERS, ms) if v == 0.0}
+    print("regnet route %s %s %s %s: count %d, no own launch: %s, ms %s"
+          % (entry, impl, hooks, shape, count.value, sorted(silent), ["%.4f" % v for v in ms]))
+    assert count.value == 1
+    assert all(v >= 0.0 for v in ms)
+    assert silent == fused_away
+
+
 @pytest.mark.parametrize("shape", [(192, 128, 160), (104, 48, 64), (40, 24, 48)])
 def test_regnet_span_and_fused_pair_equal_the_plain_schedules(shape):
     """The dominant launch's SPAN schedule (conv3d_c8.hip: workgroups own depth ranges that may cross a tile boundary) against the
