@@ -147,3 +147,77 @@ def classification_loss(reg, gt, depth_start, depth_interval):
     onehot.scatter_(0, index.clamp(0, D - 1)[None], inside[None].to(reg.dtype))
     ce = -(onehot * torch.log(prob)).sum(0)
     return (mask * ce).sum() / (mask.sum() + 1e-7)
+
+
+# ---- UNetDS2GN towers (mvsnetworks.py:53-115; conv_gn / deconv_gn network.py:217-276, 350-409) ------------------
+# Dtype-generic on purpose: run on float32 tensors the same expressions give the float32 noise floor that the device
+# tests derive their bound from (tests/test_gpu_towers_backward.py).
+
+def _pad_same2d(x, k, stride):
+    """x (V,C,H,W): TensorFlow SAME padding on the two trailing axes."""
+    pads = []
+    for n in reversed(x.shape[-2:]):
+        _, pb, pa = O.same_pad(int(n), k, stride)
+        pads += [pb, pa]
+    return F.pad(x, pads)
+
+
+def _conv2d_nchw(x, w, stride):
+    return F.conv2d(_pad_same2d(x, int(w.shape[0]), stride), w.permute(3, 2, 0, 1), stride=stride)
+
+
+def _deconv2d_nchw(x, w, stride=2):
+    k = int(w.shape[0])
+    y = F.conv_transpose2d(x, w.permute(3, 2, 0, 1), stride=stride)
+    H, W = x.shape[-2:]
+    pb_h, pb_w = O.same_pad(stride * H, k, stride)[1], O.same_pad(stride * W, k, stride)[1]
+    return y[..., pb_h:pb_h + stride * H, pb_w:pb_w + stride * W]
+
+
+def _gn_relu_nchw(x, gamma, beta, relu, eps=1e-5):
+    y = F.group_norm(x, max(1, x.shape[1] // 8), gamma, beta, eps=eps)
+    return F.relu(y) if relu else y
+
+
+def conv2d_same(x, w, stride):
+    """x (V,H,W,Cin), w TF layout (k,k,Cin,Cout) -> (V,ceil(H/stride),ceil(W/stride),Cout): tf.layers.conv2d SAME, no bias."""
+    return _conv2d_nchw(x.permute(0, 3, 1, 2), w, stride).permute(0, 2, 3, 1)
+
+
+def deconv2d_same(x, w):
+    """x (V,H,W,Cin), w TF layout (3,3,Cout,Cin) -> (V,2H,2W,Cout): tf.layers.conv2d_transpose SAME stride 2, no bias."""
+    return _deconv2d_nchw(x.permute(0, 3, 1, 2), w).permute(0, 2, 3, 1)
+
+
+def group_norm_relu(x, gamma, beta, relu):
+    """x (V,H,W,C): per view, groups of 8 channels, biased variance, eps 1e-5 (network.py:239-273), then ReLU if `relu`."""
+    return _gn_relu_nchw(x.permute(0, 3, 1, 2), gamma, beta, relu).permute(0, 2, 3, 1)
+
+
+def unet_layer(name, kind, x, p, k, stride):
+    """One row of O.UNET_LAYERS on x (V,C,H,W): 'cg' conv + GroupNorm + ReLU, 'dg' transposed conv + GroupNorm, 'c' conv."""
+    if kind == "dg":
+        return _gn_relu_nchw(_deconv2d_nchw(x, p["w"], stride), p["gamma"], p["beta"], False)
+    y = _conv2d_nchw(x, p["w"], stride)
+    return _gn_relu_nchw(y, p["gamma"], p["beta"], True) if kind == "cg" else y
+
+
+def unet_ds2gn(images, p, layer=unet_layer):
+    """images (V,H,W,3), p[name] = {'w','gamma','beta'} tensors in the TensorFlow layouts ('w' only for conv10_2) ->
+    (V,H/4,W/4,32), differentiable in images and p.  `layer`: what computes one row of the table -- the sensitivity tests
+    (tests/test_towers_oracle_host.py) substitute a deliberately wrong one for a single layer."""
+    layers = {"data": images.permute(0, 3, 1, 2)}
+    for name, kind, srcs, k, _mult, stride in O.UNET_LAYERS:
+        x = layers[srcs[0]] if len(srcs) == 1 else torch.cat([layers[s] for s in srcs], 1)
+        layers[name] = layer(name, kind, x, p[name], k, stride)
+    return layers["conv10_2"].permute(0, 2, 3, 1)
+
+
+def unet_ds2gn_gradients(images, params, g, dtype=torch.float64, layer=unet_layer):
+    """numpy images (V,H,W,3), params[name][key], g (V,H/4,W/4,32) -> (features, {(name, key): gradient of sum(features * g)})
+    as numpy arrays, everything computed in `dtype`."""
+    mk = lambda a, grad=False: torch.tensor(np.asarray(a), dtype=dtype).requires_grad_(grad)
+    p = {name: {key: mk(v, True) for key, v in d.items()} for name, d in params.items()}
+    f = unet_ds2gn(mk(images), p, layer)
+    (f * mk(g)).sum().backward()
+    return f.detach().numpy(), {(name, key): t.grad.numpy() for name, d in p.items() for key, t in d.items()}

@@ -66,3 +66,11 @@ def run_ranks(code, env, world=2, timeout=300):
         outs.append((p.returncode, fo.read(), fe.read()))
         fo.close(); fe.close()
     return outs
+
+
+def tensor_distance(got, ref64):
+    """max |got - ref64| / max |ref64|: how far a tensor is from its float64 reference, in units of the reference's largest
+    entry.  The tower tests measure the float32 CPU oracle with it and hold the device to a multiple of that."""
+    got, ref64 = np.asarray(got, np.float64), np.asarray(ref64, np.float64)
+    assert got.shape == ref64.shape, (got.shape, ref64.shape)
+    return float(np.abs(got - ref64).max() / np.abs(ref64).max())

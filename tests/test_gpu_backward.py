@@ -228,6 +228,78 @@ def test_rmsprop_step_matches_tensorflow_formula():
     assert np.allclose(n(mst), ms, rtol=1e-5)
 
 
+def _optimizer_steps(kind, nel, steps, momentum=0.9, pad=0):
+    """`steps` updates of one optimiser kernel on `nel` elements of buffers `pad` elements longer, against the float64 formulas
+    of TensorFlow's update ops (include/mvsnet_hip.h) on the same inputs: the hyper-parameters the kernels receive are float32, so
+    the formulas take their float32 values (1 - float32(0.999) is 1.3e-5 away from 0.001).  Returns [(name, got, expected)], the
+    padding included (expected: untouched)."""
+    import math
+    from mvsnet_amd import _lib as L
+    lib = L.load()
+    rs = np.random.RandomState(nel % 1000 + len(kind))
+    f32 = lambda v: float(np.float32(v))
+    tot = nel + pad
+    w, g = rs.randn(tot).astype(np.float32), rs.randn(tot).astype(np.float32)
+    first = np.ones(tot, np.float32) if kind == "rmsprop" else np.zeros(tot, np.float32)      # TF: the rms slot starts at one
+    second = np.zeros(tot, np.float32)
+    wt, gt, at, bt = t(w), t(g), t(first), t(second)
+    w, a, b = w.astype(np.float64), first.astype(np.float64), second.astype(np.float64)
+    gs = g.astype(np.float64)[:nel] * 0.5
+    lr, scale, st = 1e-3, 0.5, L.stream_ptr()
+    for step in range(steps):
+        if kind == "rmsprop":
+            decay, eps = 0.9, 1e-10
+            L.check(lib.mvs_rmsprop_step_f32(L.ptr(wt), L.ptr(gt), L.ptr(at), L.ptr(bt), nel, lr, decay, momentum, eps, scale, st))
+            a[:nel] += (gs * gs - a[:nel]) * (1 - f32(decay))
+            b[:nel] = f32(momentum) * b[:nel] + f32(lr) * gs / np.sqrt(a[:nel] + f32(eps))
+            w[:nel] -= b[:nel]
+        elif kind == "momentum":
+            L.check(lib.mvs_momentum_step_f32(L.ptr(wt), L.ptr(gt), L.ptr(at), nel, lr, momentum, scale, st))
+            a[:nel] = f32(momentum) * a[:nel] + gs
+            w[:nel] -= f32(lr) * a[:nel]
+        else:
+            tt = step + 1                                                    # Trainer.apply_gradients: global_step + 1
+            lr_t = lr * math.sqrt(1.0 - 0.999 ** tt) / (1.0 - 0.9 ** tt)
+            L.check(lib.mvs_adam_step_f32(L.ptr(wt), L.ptr(gt), L.ptr(at), L.ptr(bt), nel, lr_t, 0.9, 0.999, 1e-8, scale, st))
+            a[:nel] += (gs - a[:nel]) * (1 - f32(0.9))
+            b[:nel] += (gs * gs - b[:nel]) * (1 - f32(0.999))
+            w[:nel] -= f32(lr_t) * a[:nel] / (np.sqrt(b[:nel]) + f32(1e-8))
+    out = [("w", n(wt), w), ("slot0", n(at), a)]
+    if kind != "momentum":
+        out.append(("slot1", n(bt), b))
+    return out
+
+
+def _assert_optimizer(res, nel):
+    for name, got, exp in res:
+        assert np.array_equal(got[nel:], exp[nel:]), name                    # nothing beyond n is touched
+        if name == "w":
+            assert np.allclose(got[:nel], exp[:nel], rtol=1e-5, atol=1e-7), (name, np.abs(got[:nel] - exp[:nel]).max())
+        else:
+            assert np.allclose(got[:nel], exp[:nel], rtol=1e-5, atol=0), (name, (np.abs(got[:nel] - exp[:nel]) / np.abs(exp[:nel])).max())
+
+
+@pytest.mark.parametrize("kind", ["momentum", "adam"])
+def test_momentum_and_adam_steps_match_the_tensorflow_formulas(kind):
+    """mvs_momentum_step_f32 / mvs_adam_step_f32: three steps with lr_t formed as Trainer.apply_gradients forms it."""
+    _assert_optimizer(_optimizer_steps(kind, 10007, 3), 10007)
+
+
+def test_rmsprop_step_with_momentum_matches_tensorflow_formula():
+    """momentum = 0.9: the `mom` slot feeds back (the trainer runs with 0, where it is only the last update)."""
+    res = _optimizer_steps("rmsprop", 10007, 3, momentum=0.9)
+    assert [r[0] for r in res] == ["w", "slot0", "slot1"]                     # w, ms, mom
+    _assert_optimizer(res, 10007)
+
+
+@pytest.mark.parametrize("kind", ["rmsprop", "momentum", "adam"])
+def test_optimizer_steps_beyond_one_trip_of_the_grid(kind):
+    """n above grid_for's cap of 4096 workgroups x 256 threads: the grid-stride loop takes a second, partial trip; the 61
+    elements behind n stay as they were."""
+    nel = 4096 * 256 + 4099
+    _assert_optimizer(_optimizer_steps(kind, nel, 1, pad=61), nel)
+
+
 def _train_batch(N=3, H=64, W=96, D=16):
     images = S.make_images(N, H, W, seed=0)
     cams = S.make_cams(N, H // 4, W // 4, D)
