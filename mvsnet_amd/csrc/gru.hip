@@ -562,6 +562,9 @@ int launch_conv2d(const float* xa, int Ca, const float* xb, int Cb, const float*
 #define MVS_C2D(CO) case CO: conv2d_cat_kernel<CO><<<grid, 256, 0, st>>>(xa, Ca, xb, Cb, w, bias, H, W, y, stats, groups); break;
     switch (Cout) {
         MVS_C2D(1) MVS_C2D(2) MVS_C2D(4) MVS_C2D(8) MVS_C2D(16) MVS_C2D(32)
+        // filter counts off the reference's powers of two, and the 'fat' variant's 32-filter cell 1 (a 64-channel gate convolution):
+        // mvs_gru_wta*_f32 accepts every f <= 64, and these were MVS_E_SHAPE half-way into its first plane
+        MVS_C2D(3) MVS_C2D(6) MVS_C2D(12) MVS_C2D(24) MVS_C2D(64)
         default: return MVS_E_SHAPE;
     }
 #undef MVS_C2D

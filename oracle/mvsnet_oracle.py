@@ -546,12 +546,13 @@ def conv_gru_cell(x, h, p, dtype=np.float32):
 
 
 def winner_take_all(ref_feature, src_features, homographies, depths, gru_params,
-                    view_num=None, dtype=np.float32):
+                    view_num=None, dtype=np.float32, return_scores=False):
     """Loop body + tail of inference_winner_take_all, mvsnet/model.py:676-751.
 
     depths[d] is the depth value of plane d (model.py:706-715).  gru_params =
     {'gru1','gru2','gru3': cell params, 'prob_w' (3,3,F3,1), 'prob_b' (1,)}.
-    Returns depth_image (H,W), prob (H,W)."""
+    Returns depth_image (H,W), prob (H,W); with return_scores also the per-plane reg
+    (D,H,W) in the working dtype (the value whose exp is compared, :701-703)."""
     ref = np.asarray(ref_feature, dtype=dtype)
     src = np.asarray(src_features, dtype=dtype)
     Hs = np.asarray(homographies, dtype=dtype)
@@ -567,6 +568,7 @@ def winner_take_all(ref_feature, src_features, homographies, depths, gru_params,
     exp_sum = np.zeros((Hh, W), dtype)
     depth_image = np.zeros((Hh, W), dtype)
     max_prob = np.zeros((Hh, W), dtype)                               # :663-673
+    scores = []
     for d in range(D):
         warped = [tf_transform_homography(src[v], Hs[v, d], dtype) for v in range(n_src)]
         cost = variance_cost_eager(ref, warped, view_num, dtype)      # :680-693
@@ -575,11 +577,16 @@ def winner_take_all(ref_feature, src_features, homographies, depths, gru_params,
         s3 = conv_gru_cell(s2, s3, gru_params["gru3"], dtype)         # :700
         reg = conv2d_same(s3, gru_params["prob_w"], 1, gru_params["prob_b"], dtype)[..., 0]  # :701-702
         prob = np.exp(reg).astype(dtype)                              # :703
+        if return_scores:
+            scores.append(reg)
         upd = max_prob < prob                                         # :721-722 (strict <)
         max_prob = np.where(upd, prob, max_prob)
         depth_image = np.where(upd, dtype(depths[d]), depth_image)
         exp_sum = exp_sum + prob                                      # :731
-    return depth_image.astype(dtype), (max_prob / (exp_sum + dtype(1e-7))).astype(dtype)  # :749-751
+    out = depth_image.astype(dtype), (max_prob / (exp_sum + dtype(1e-7))).astype(dtype)  # :749-751
+    if return_scores:
+        return out + (np.stack(scores).astype(dtype),)
+    return out
 
 
 def wta_depths(depth_num, depth_start, depth_end, inverse_depth=False, dtype=np.float32):
@@ -809,8 +816,9 @@ def inference_mem_from_features(features, cams, depth_num, depth_start, depth_in
 
 
 def inference_winner_take_all_from_features(features, cams, depth_num, depth_start, depth_end,
-                                            gru_params, inverse_depth=False, dtype=np.float32):
-    """mvsnet/model.py:601-751 after the feature towers."""
+                                            gru_params, inverse_depth=False, dtype=np.float32,
+                                            return_scores=False):
+    """mvsnet/model.py:601-751 after the feature towers.  return_scores: see winner_take_all."""
     feats = np.asarray(features, dtype=dtype)
     N = feats.shape[0]
     D = int(depth_num)
@@ -822,7 +830,8 @@ def inference_winner_take_all_from_features(features, cams, depth_num, depth_sta
             interval = (dtype(depth_end) - dtype(depth_start)) / (dtype(D) - dtype(1))
             Hs.append(get_homographies(cams[0], cams[v], D, depth_start, interval, dtype))
     depths = wta_depths(D, depth_start, depth_end, inverse_depth, dtype)
-    return winner_take_all(feats[0], feats[1:], np.stack(Hs), depths, gru_params, N, dtype)
+    return winner_take_all(feats[0], feats[1:], np.stack(Hs), depths, gru_params, N, dtype,
+                           return_scores)
 
 
 # --------------------------------------------------------------------------------------

@@ -2,6 +2,11 @@
 
 All calls go through the C ABI (ctypes) of libmvsnet_hip.so.  Tolerances are stated per test;
 the north-star bar is 1e-3 relative L1 on the depth map, the kernels are held to ~1e-5.
+
+The recurrent sweep is held pixel by pixel: besides the older arg-max share (97-98 % equal winners, prob of those to 2e-4 .. 5e-4)
+every pixel of every sweep test goes through sweep_reference.check_every_pixel against the float64 oracle's per-plane scores --
+the chosen plane within 4 E of the best, prob within 4 E of max/sum, E = the float32 oracle's own distance from float64 (about
+1e-5 at these sizes); every kernel route is held the same way in tests/test_gpu_sweep_every_pixel.py.
 """
 import numpy as np
 import pytest
@@ -10,6 +15,8 @@ import torch
 from oracle import mvsnet_oracle as O
 from mvsnet_amd import synthetic as S
 from mvsnet_amd import _lib as L
+
+from tests import sweep_reference as SR
 
 pytestmark = pytest.mark.gpu
 
@@ -658,6 +665,7 @@ def test_gru_wta_pipelined_sweep_with_ragged_depth_matches_oracle():
     same = np.abs(depth - ed) <= 1e-6 * np.abs(ed)
     assert same.mean() > 0.97, same.mean()
     np.testing.assert_allclose(prob[same], ep[same], rtol=5e-4)
+    SR.check_every_pixel(depth, prob, SR.plane_scores(w.features, cams, D, w.depth_start, end, gp, False), "toy D=37")
     # and it is reproducible run to run
     d2, p2 = inference_winner_take_all(None, t(cams)[None], D, w.depth_start, end, weights=weights, features=t(w.features))
     assert np.array_equal(n(d2)[0, :, :, 0], depth) and np.array_equal(n(p2)[0, :, :, 0], prob)
@@ -681,6 +689,8 @@ def test_gru_wta_matches_oracle(inverse, mode):
     same = np.abs(depth - ed) <= 1e-6 * np.abs(ed)
     assert same.mean() > 0.98
     np.testing.assert_allclose(prob[same], ep[same], rtol=2e-4)
+    SR.check_every_pixel(depth, prob, SR.plane_scores(w.features, w.cams, w.depth_num, w.depth_start, w.depth_end, gp, inverse),
+                         "toy %s inverse=%s" % (mode, inverse))
 
 
 @pytest.mark.parametrize("hw", [(27, 41), (9, 47), (31, 17)])
@@ -702,6 +712,8 @@ def test_gru_wta_ragged_image_sizes_match_oracle(hw):
     same = np.abs(depth - ed) <= 1e-6 * np.abs(ed)
     assert same.mean() > 0.97, same.mean()
     np.testing.assert_allclose(prob[same], ep[same], rtol=5e-4)
+    ref = SR.plane_scores(feats, w.cams, w.depth_num, w.depth_start, w.depth_end, gp, False)
+    SR.check_every_pixel(depth, prob, ref, "small %dx%d" % hw)
     # the wavefront kernels of rounds 3-4 on the same input: the same planes up to ties
     import ctypes as C
     from mvsnet_amd import _lib as L
@@ -713,6 +725,7 @@ def test_gru_wta_ragged_image_sizes_match_oracle(hw):
     finally:
         L.check(lib.mvs_gru_set_formulation(0), "mvs_gru_set_formulation")
     assert (n(d1)[0, :, :, 0] == depth).mean() > 0.97
+    SR.check_every_pixel(n(d1)[0, :, :, 0], n(_p1)[0, :, :, 0], ref, "small %dx%d, wavefront" % hw)
 
 
 # ---- R10 end to end -------------------------------------------------------------------------------------
@@ -781,6 +794,8 @@ def test_device_matches_committed_golden_fixtures():
                                             weights=weights, features=t(w.features))
     d = n(depth)[0, :, :, 0]
     assert (np.abs(d - g["depth"]) <= 1e-6 * g["depth"]).mean() > 0.98
+    SR.check_every_pixel(d, n(prob)[0, :, :, 0], SR.plane_scores(w.features, w.cams, w.depth_num, w.depth_start, w.depth_end, gp, False),
+                         "toy, golden fixture's input")
 
 
 def test_gru_batch_entry_point_argument_checks_and_ragged_batches():
@@ -809,6 +824,7 @@ def test_gru_batch_entry_point_argument_checks_and_ragged_batches():
         same = d[v] == ed.astype(np.float32)
         assert same.mean() > 0.97, (v, float(same.mean()))
         assert np.abs(p[v][same] - ep[same]).max() < 2e-4
+        SR.check_every_pixel(d[v], p[v], SR.plane_scores(feats[v], w.cams, D, w.depth_start, ends[v], gp, False), "batch of 8, view %d" % v)
     # argument checks
     lib = _lib.load()
     g = weights.gru
