@@ -212,7 +212,7 @@ int mvs_deconv3d_scalar(const float* x, const float* xs, const float* xb, const 
 // plane homographies + zero-fill of `zero_n` doubles in one launch (homography.hip)
 int mvs_homography_transforms_zero(const float* cams, int view_num, int depth_num, float depth_start, float depth_interval,
                                    float depth_end, int inverse_depth, float* transforms, double* zero, int zero_n, hipStream_t st);
-// one side stream + fork / join events of the caller's stream set (gru.hip, mvs_gru_prepare); false without a set
+// one side stream + fork / join events of the caller's stream set (gru_streams.hip, mvs_gru_prepare); false without a set
 bool mvs_stream_set_side(hipStream_t caller, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);
 int mvs_conv3d_s2_mfma(const ConvArgs& a, int Cin, int Cout, hipStream_t st);
 int mvs_deconv3d_mfma_launch(const ConvArgs& a, int Cin, int Cout, hipStream_t st);

@@ -3,7 +3,7 @@
 //
 // The recurrence couples cell k of plane d only to cell k-1 of plane d and to cell k of plane d-1, and every convolution
 // of a cell is followed by a whole-image LayerNorm (convgru.py:30-31) -- a global barrier.  Rounds 2-4 ran the three cells
-// as a wavefront over four HIP streams (gru.hip): ~7 launches per plane, cross-stream events per group of planes, and
+// as a wavefront over four HIP streams (gru_sweep.hip): ~7 launches per plane, cross-stream events per group of planes, and
 // 136 KB cell-1 workgroups that time-share the CUs with 26 KB small-cell workgroups (round-4 device trace: the median
 // cell-1 workgroup starts 34-53 us late, a plane costs the SUM of its kernels).  Here the cells are skewed by one plane
 // each instead, so that everything between two LayerNorm barriers is one launch:
@@ -29,20 +29,13 @@
 //   C: waves 0-1 cell 2 candidate, waves 2-3 cell 3 candidate
 // so that each SIMD's matrix pipe carries one large and one small job beside its two cell-1 rows.
 #include "conv_common.h"
+#include "gru_common.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace {
 
-constexpr int FMAXV = 8;                 // reference views per launch (mvs_gru_wta_batch_f32)
 constexpr int FNT = 512, FTH = 8, FTW = 16, FPW = FTW + 2, FNPOS = (FTH + 2) * FPW;      // 180 staged positions per tile
-
-// Copies of a plane's LayerNorm sums: every workgroup of a launch adds its partial sums with float64 atomics, and atomics on one
-// cache line are performed one after the other by the L2 -- 256 workgroups x 3 cells on the same 144 bytes were 6 us of every
-// plane (round 6: a build without these atomics ran the c3 sweep in 20.87 instead of 22.41 ms; tools/r6_gru_nostat_diag.patch).
-// A workgroup adds to copy blockIdx.x % 8 (256 bytes apart: other lines); the next launch's prologue adds the copies up.
-constexpr int GRU_FUSED_SLOTS = 8;
-constexpr int GRU_FUSED_SLOT_STRIDE = 32;
 
 struct FusedCell {
     // byte offsets inside the view's workspace block (every activation tensor of the sweep lives in it)
@@ -69,7 +62,7 @@ struct FusedArgs {
     long long* trace;       // diagnostic (null in the product): [0] = record counter, then 8 x int64 per workgroup (mvs_gru_fused_trace)
     int trace_cap, launch_id;
 };
-struct FusedDepth { float v[FMAXV]; };   // depth value of the WTA plane, per view (its own kernel argument: indexed on the kernarg)
+struct FusedDepth { float v[MVS_GRU_MAX_VIEWS]; };   // depth value of the WTA plane, per view (its own kernel argument: indexed on the kernarg)
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -630,24 +623,16 @@ int launch_fused(const FusedArgs& a0, const FusedDepth& dv, int views, bool stea
     a.wg_per_view = per;
     constexpr int S = PHASE == 0 ? 56 : 72;
     constexpr int COUT = PHASE == 0 ? 32 : 16;
-    constexpr int WS_FLOATS = PHASE == 0 ? 2 * 720 + 288 + 20 : 720 + 288;
+    constexpr int WS_FLOATS = PHASE == 0 ? GRU_FUSED_WSG_FLOATS : GRU_FUSED_WSC_FLOATS;
     const size_t smem = (size_t)(9 * 48 * COUT + WS_FLOATS + 2 * FNPOS * S + (PHASE == 1 ? 3 * FNPOS * 4 : 0)) * sizeof(float);
     return steady ? launch_fused2<PHASE, true>(a, dv, per * views, smem, st) : launch_fused2<PHASE, false>(a, dv, per * views, smem, st);
 }
 
 }  // namespace
 
-// ---- host side of the fused sweep (called from mvs_gru_wta_batch_f32, gru.hip) -------------------------------------------
-// Workspace of one view as the fused sweep sees it (carved by gru.hip): S[k][2] state ping-pong, G[k][2] gate ping-pong, Cb[k]
-// candidate, stats (a ring of planes x GRU_FUSED_SLOTS copies x 3 cells x 6 doubles), x (a batch of XB cost slices).
-struct GruFusedWs {
-    char* base;                              // view 0's workspace block (everything below lies inside it)
-    float* x; float* S[3][2]; float* G[3][2]; float* Cb[3]; double* stats;
-    float *max_prob, *depth, *exp_sum;
-    float *w1g, *w1c, *wsg, *wsc;            // prepared weights (shared by the views; view 0's block)
-};
-constexpr int GRU_FUSED_RING = 64;           // LayerNorm-sum rows: plane p uses row p % 64 (gru.hip zeroes them a batch ahead)
-constexpr int GRU_FUSED_ROW = GRU_FUSED_SLOT_STRIDE * GRU_FUSED_SLOTS;      // doubles per row: [slot][cell][6] (the same constants as in gru.hip)
+// ---- host side of the fused sweep (called from fused_sweep, gru_sweep.hip) -----------------------------------------------
+// Workspace of one view as the fused sweep sees it (GruWs, gru_common.h): h[k][0..1] state ping-pong, {g[k], g2[k]} gate ping-pong,
+// c[k] candidate, fstats (a ring of planes x GRU_FUSED_SLOTS copies x 3 cells x 6 doubles), x (a batch of XB cost slices).
 
 namespace {
 __global__ void gru_prob_table_kernel(const float* __restrict__ pw, const float* __restrict__ pb, float* __restrict__ out) {
@@ -656,15 +641,15 @@ __global__ void gru_prob_table_kernel(const float* __restrict__ pw, const float*
 }
 }  // namespace
 
-int mvs_gru_fused_prepare_weights(const float* const* params, const GruFusedWs& ws, hipStream_t st) {
+int mvs_gru_fused_prepare_weights(const float* const* params, const GruWs& ws, hipStream_t st) {
     // small tables.  G: cell 2 gates (20 -> 8) as two output-channel quads, cell 3 gates (6 -> 4), prob_conv.  C: cell 2 candidate
     // (20 -> 4), cell 3 candidate (6 -> 2).
     auto tab = [&](const float* w, int CT, int CO, int co0, int nquad, float* out) {
         gru_small_table_kernel<<<mvs_cdiv(9 * nquad * 16, 256), 256, 0, st>>>(w, CT, CO, co0, nquad, out);
     };
-    tab(params[10], 20, 8, 0, 5, ws.wsg); tab(params[10], 20, 8, 4, 5, ws.wsg + 720); tab(params[20], 6, 4, 0, 2, ws.wsg + 1440);
-    gru_prob_table_kernel<<<1, 64, 0, st>>>(params[30], params[31], ws.wsg + 1728);
-    tab(params[16], 20, 4, 0, 5, ws.wsc); tab(params[26], 6, 2, 0, 2, ws.wsc + 720);
+    tab(params[10], 20, 8, 0, 5, ws.wsg); tab(params[10], 20, 8, 4, 5, ws.wsg + GRU_FUSED_WSG_C2HI); tab(params[20], 6, 4, 0, 2, ws.wsg + GRU_FUSED_WSG_C3);
+    gru_prob_table_kernel<<<1, 64, 0, st>>>(params[30], params[31], ws.wsg + GRU_FUSED_WSG_PROB);
+    tab(params[16], 20, 4, 0, 5, ws.wsc); tab(params[26], 6, 2, 0, 2, ws.wsc + GRU_FUSED_WSC_C3);
     return (int)hipGetLastError();
 }
 
@@ -677,13 +662,14 @@ extern "C" int mvs_gru_fused_trace(void* buffer, int capacity) {
 }
 
 // one plane step of the pipeline: G(t) then C(t).  t runs 0 .. depth_num + 2.
-int mvs_gru_fused_step(const GruFusedWs& ws, const float* const* params, int t, int depth_num, const float* x_t, int H, int W,
+int mvs_gru_fused_step(const GruWs& ws, char* base, const float* const* params, int t, int depth_num, const float* x_t, int H, int W,
                        int views, size_t vstride, const float* depth_values /* host, (views, depth_num) */, hipStream_t st) {
     if (vstride >= ((size_t)1 << 31)) return MVS_E_SHAPE;            // the kernels address a view's block with 32-bit byte offsets
-    auto off = [&](const void* p) { return (unsigned)((const char*)p - ws.base); };
+    auto off = [&](const void* p) { return (unsigned)((const char*)p - base); };
+    auto G = [&](int k, int i) { return (i & 1) ? ws.g2[k] : ws.g[k]; };      // gate ping-pong
     FusedArgs g = {}, c = {};
     g.x = c.x = off(x_t);
-    g.ws = c.ws = ws.base;
+    g.ws = c.ws = base;
     g.H = c.H = H; g.W = c.W = W; g.vstride = c.vstride = vstride;
     bool steady = true;                              // every cell live and blending, the WTA update on
     for (int k = 0; k < 3; ++k) {
@@ -693,29 +679,29 @@ int mvs_gru_fused_step(const GruFusedWs& ws, const float* const* params, int t, 
         steady = steady && conv && blend;
         const int pc = p < 0 ? 0 : p, pm = p < 1 ? 0 : p - 1;        // clamped plane indices for the stats rows of dead cells
         FusedCell& gc = g.cell[k];
-        // s(q) lives in S[k][q & 1] (s(-1) = 0 in S[k][1]); G forms s(p-1) from s(p-2)
-        gc.h = off(blend ? ws.S[k][p & 1] : ws.S[k][(p - 1) & 1]);
-        gc.c = off(ws.Cb[k]); gc.g = off(ws.G[k][(p - 1) & 1]);
-        gc.st_in = ws.stats + (size_t)(pm % GRU_FUSED_RING) * GRU_FUSED_ROW + k * 6;
-        gc.h_out = off(ws.S[k][(p - 1) & 1]);
-        gc.y = off(ws.G[k][p & 1]);
-        gc.st_out = ws.stats + (size_t)(pc % GRU_FUSED_RING) * GRU_FUSED_ROW + k * 6;
+        // s(q) lives in h[k][q & 1] (s(-1) = 0 in h[k][1]); G forms s(p-1) from s(p-2)
+        gc.h = off(blend ? ws.h[k][p & 1] : ws.h[k][(p - 1) & 1]);
+        gc.c = off(ws.c[k]); gc.g = off(G(k, p - 1));
+        gc.st_in = gru_fused_row(ws, pm) + k * 6;
+        gc.h_out = off(ws.h[k][(p - 1) & 1]);
+        gc.y = off(G(k, p));
+        gc.st_out = gru_fused_row(ws, pc) + k * 6;
         gc.bias = pp[1]; gc.ga = pp[4]; gc.gb = pp[5]; gc.oa = pp[8]; gc.ob = pp[9];
         gc.conv = conv; gc.blend = blend;
         FusedCell& cc = c.cell[k];
-        cc.h = off(ws.S[k][(p - 1) & 1]); cc.c = 0; cc.g = off(ws.G[k][p & 1]);
-        cc.st_in = ws.stats + (size_t)(pc % GRU_FUSED_RING) * GRU_FUSED_ROW + k * 6;
-        cc.h_out = 0; cc.y = off(ws.Cb[k]); cc.st_out = ws.stats + (size_t)(pc % GRU_FUSED_RING) * GRU_FUSED_ROW + k * 6;
+        cc.h = off(ws.h[k][(p - 1) & 1]); cc.c = 0; cc.g = off(G(k, p));
+        cc.st_in = gru_fused_row(ws, pc) + k * 6;
+        cc.h_out = 0; cc.y = off(ws.c[k]); cc.st_out = gru_fused_row(ws, pc) + k * 6;
         cc.bias = pp[7]; cc.ga = pp[2]; cc.gb = pp[3]; cc.oa = pp[2]; cc.ob = pp[3];
         cc.conv = conv; cc.blend = 0;
     }
-    g.w1 = ws.w1g; g.wsmall = ws.wsg; c.w1 = ws.w1c; c.wsmall = ws.wsc;
+    g.w1 = ws.wfg; g.wsmall = ws.wsg; c.w1 = ws.wfo; c.wsmall = ws.wsc;
     g.max_prob = off(ws.max_prob); g.depth_image = off(ws.depth); g.exp_sum = off(ws.exp_sum);
     const int q = t - 3;
     g.wta = q >= 0 && q < depth_num;
     steady = steady && g.wta;
     FusedDepth dv = {};
-    for (int v = 0; v < views && v < FMAXV; ++v) dv.v[v] = g.wta ? depth_values[(size_t)v * depth_num + q] : 0.f;
+    for (int v = 0; v < views && v < MVS_GRU_MAX_VIEWS; ++v) dv.v[v] = g.wta ? depth_values[(size_t)v * depth_num + q] : 0.f;
     g.trace = c.trace = g_fused_trace; g.trace_cap = c.trace_cap = g_fused_trace_cap;
     g.launch_id = g_fused_launch++; c.launch_id = g_fused_launch++;
     int rc = launch_fused<0>(g, dv, views, steady, st);

@@ -16,6 +16,7 @@
 // side stream, and the per-plane kernels on the critical path only convolve the 16 state channels (CA = 0) and
 // add the precomputed part in their epilogue (ADD).  See mvs_gru_wta_f32.
 #include "conv_common.h"
+#include "gru_common.h"
 #include <type_traits>
 
 namespace {

@@ -269,3 +269,19 @@ def test_test_hooks_and_fused_route_without_a_gpu(lib_built):
     assert blk(300, 400) < 2 ** 31 and h.mvs_gru_fused_route(32, 16, 4, 2, blk(300, 400)) == 1
     assert blk(384, 576) >= 2 ** 31 and h.mvs_gru_fused_route(32, 16, 4, 2, blk(384, 576)) == 0
     assert h.mvs_gru_fused_route(32, 32, 8, 4, blk(300, 400)) == 0 and h.mvs_gru_fused_route(16, 16, 4, 2, blk(300, 400)) == 0
+
+
+def test_gru_workspace_layout_is_pinned(lib_built):
+    """mvs_gru_workspace_bytes (H, W, C, f1, f2, f3) -> bytes per view block, as commit 5de61d1 (the last one with the sweep
+    inside csrc/gru.hip) returned them: mvsnet_amd/model.py allocates by this number and the fused kernels address the block
+    with 32-bit offsets from its base, so a change of the carving is a change of the ABI."""
+    from mvsnet_amd import _lib
+    h = _lib.load()
+    pinned = {(300, 400, 32, 16, 4, 2): 1222399744,      # 5de61d1
+              (384, 576, 32, 16, 4, 2): 2252857600,      # 5de61d1
+              (5, 11, 32, 16, 4, 2): 885504,             # 5de61d1
+              (27, 41, 16, 8, 2, 1): 5850368,            # 5de61d1
+              (27, 41, 64, 32, 8, 4): 23356928,          # 5de61d1
+              (27, 41, 16, 12, 6, 3): 8543488}           # 5de61d1
+    for shape, want in pinned.items():
+        assert h.mvs_gru_workspace_bytes(*shape) == want, shape
