@@ -6,8 +6,14 @@ gamma, beta) -> ReLU), :350-409 (deconv_gn: no ReLU) and :171-215 (plain conv fo
 all with TensorFlow 'SAME' padding (asymmetric for stride 2).  It produces the hot path's input;
 the HIP towers for inference are feature_net_hip.HipUNetDS2GN; this module
 is the fallback-free PyTorch-ROCm tower that training differentiates (north_star keeps it on torch).
+
+`tower_layers` is the layer table the HIP towers read (feature_net_hip, feature_net_train): UNET_LAYERS with channel counts,
+sizes and the route of each layer's input gradient.  `UNetDS2GN` / `unet_forward` stay on UNET_LAYERS alone: they are the
+independent cross-check of those modules.
 """
 from __future__ import annotations
+
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -37,42 +43,85 @@ UNET_LAYERS = (
 )
 
 
+# a layer's variables in the order trainers flatten them (conv10_2 has no GroupNorm)
+UNET_VARIABLES = tuple((name, ("w",) if kind == "c" else ("w", "gamma", "beta")) for name, kind, *_ in UNET_LAYERS)
+
+# how the training towers take a layer's input gradient (feature_net_train): not at all (the layer reads the image), through
+# ATen, or on the forward HIP kernels -- stride-1 convolution with the mirrored kernel, stride-2 convolution with the same
+# array (transposed layers), transposed convolution with the same array (stride-2 layers)
+GX_NONE, GX_ATEN, GX_CONV_S1, GX_CONV_S2, GX_DECONV = "none", "aten", "conv_s1_mirrored", "conv_s2", "deconv"
+_GX_LAUNCH = {GX_CONV_S1: ("c", 1), GX_CONV_S2: ("c", 2), GX_DECONV: ("dg", 2)}          # route -> kind, stride of the launch
+
+
+class TowerLayer(NamedTuple):
+    """One row of UNET_LAYERS with its channel counts.  `cins`: input channels per source (`cin_tot` their sum); `relu`: whether
+    the consumers of this layer apply ReLU behind its GroupNorm; `gx`: for the three HIP routes the launch that computes the
+    input gradient from the output gradient, as a layer of its own (Cout -> cin_tot channels), else None."""
+    name: str
+    kind: str
+    srcs: tuple
+    k: int
+    stride: int
+    cins: tuple
+    cin_tot: int
+    cout: int
+    relu: int
+    gx_route: str = GX_NONE
+    gx: Optional["TowerLayer"] = None
+
+    def out_size(self, h, w):
+        return (2 * h, 2 * w) if self.kind == "dg" else (-(-h // self.stride), -(-w // self.stride))
+
+
+def tower_layers(cout_of, image_channels=4):
+    """The layer table: `cout_of(name, kind, mult)` gives a layer's output channels (from its kernel's shape, or from a base
+    filter count); the image counts `image_channels` (4 where the HIP kernels read it: padded 3 -> 4)."""
+    chans, table = {"data": image_channels}, []
+    for name, kind, srcs, k, mult, stride in UNET_LAYERS:
+        cins = tuple(chans[s_] for s_ in srcs)
+        cin_tot, cout = sum(cins), int(cout_of(name, kind, mult))
+        chans[name] = cout
+        if srcs == ("data",):
+            route = GX_NONE
+        elif k != 3 or cin_tot % 8:                        # the two 5 x 5 stride-2 layers
+            route = GX_ATEN
+        else:
+            route = GX_CONV_S2 if kind == "dg" else (GX_CONV_S1 if stride == 1 else GX_DECONV)
+        gx_kind, gx_stride = _GX_LAUNCH.get(route, (None, 0))
+        gx = TowerLayer(name, gx_kind, (name,), 3, gx_stride, (cout,), cout, cin_tot, 0) if gx_kind else None
+        table.append(TowerLayer(name, kind, srcs, k, stride, cins, cin_tot, cout, 1 if kind == "cg" else 0, route, gx))
+    return tuple(table)
+
+
+def tower_layers_of(weights):
+    """The table for kernels in TensorFlow layouts, `weights[name]` = conv (k,k,Cin,Cout) / transposed conv (k,k,Cout,Cin)."""
+    return tower_layers(lambda name, kind, _mult: weights[name].shape[2 if kind == "dg" else 3])
+
+
+def layer_sizes(layers, H, W):
+    """(input h, input w, output h, output w) of every layer of the table for an H x W image."""
+    size, rows = {"data": (H, W)}, []
+    for l in layers:
+        h, w = size[l.srcs[0]]
+        size[l.name] = l.out_size(h, w)
+        rows.append((h, w) + size[l.name])
+    return rows
+
+
 def unet_macs(H, W, base_filter=8, image_channels=3):
     """Algorithmic multiply-adds of one UNetDS2GN pass over one H x W image (mvsnetworks.py:53-115): every conv / transposed
     conv counted with the taps and channels the reference's layers have (a k3 s2 transposed conv touches 9/4 taps per output)."""
-    shape = {"data": (H, W, image_channels)}
-    total = 0.0
-    for name, kind, srcs, k, mult, stride in UNET_LAYERS:
-        h, w, _ = shape[srcs[0]]
-        cin = sum(shape[s_][2] for s_ in srcs)
-        cout = base_filter * mult
-        if kind == "dg":
-            ho, wo = 2 * h, 2 * w
-            total += ho * wo * 2.25 * cin * cout
-        else:
-            ho, wo = -(-h // stride), -(-w // stride)
-            total += ho * wo * k * k * cin * cout
-        shape[name] = (ho, wo, cout)
-    return total
+    return sum((macs for _name, macs, _bytes in unet_layer_work(H, W, base_filter, image_channels)), 0.0)
 
 
 def unet_layer_work(H, W, base_filter=8, image_channels=3):
     """Per layer of one UNetDS2GN pass over one H x W image: (name, multiply-adds, algorithmic bytes = every input tensor read
     once + the output written once, fp32) -- the two rooflines a layer can be priced against."""
-    shape = {"data": (H, W, image_channels)}
+    layers = tower_layers(lambda _name, _kind, mult: base_filter * mult, image_channels)
     rows = []
-    for name, kind, srcs, k, mult, stride in UNET_LAYERS:
-        h, w, _ = shape[srcs[0]]
-        cin = sum(shape[s_][2] for s_ in srcs)
-        cout = base_filter * mult
-        if kind == "dg":
-            ho, wo = 2 * h, 2 * w
-            macs = ho * wo * 2.25 * cin * cout
-        else:
-            ho, wo = -(-h // stride), -(-w // stride)
-            macs = ho * wo * k * k * cin * cout
-        shape[name] = (ho, wo, cout)
-        rows.append((name, macs, 4.0 * (h * w * cin + ho * wo * cout)))
+    for l, (h, w, ho, wo) in zip(layers, layer_sizes(layers, H, W)):
+        macs = ho * wo * (2.25 if l.kind == "dg" else l.k * l.k) * l.cin_tot * l.cout
+        rows.append((l.name, macs, 4.0 * (h * w * l.cin_tot + ho * wo * l.cout)))
     return rows
 
 

@@ -4,16 +4,21 @@
 consumer's load (csrc/unet2d.hip).  Same constructor and call signature as the PyTorch module, so
 `MVSNetWeights` can hold either; the PyTorch/MIOpen module stays as the reference implementation of
 the glue (north_star) and as the cross-check in tests.
+
+The host side reads the layer table of `feature_net.tower_layers` (channels, sizes, who applies ReLU) and launches every
+layer through `launch_layer` -- the one place under mvsnet_amd/ that calls the two entry points; the training towers
+(`feature_net_train`) use the same function for their forward pass and for the input gradients of their backward pass.
 """
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .feature_net import UNET_LAYERS
+from .feature_net import TowerLayer, layer_sizes, tower_layers_of
 
 
 # The encoder's side branches (mvsnetworks.py:66-84) depend on ONE layer of the stride-2 chain each and are only read again by the
@@ -21,6 +26,73 @@ from .feature_net import UNET_LAYERS
 # layers) instead of in line with it.
 SIDE_BRANCH = {"2dconv0_1": 0, "2dconv0_2": 0, "2dconv1_1": 1, "2dconv1_2": 1,
                "2dconv2_1": 2, "2dconv2_2": 2, "2dconv3_1": 3, "2dconv3_2": 3}      # branch index; stream = index % side_streams
+
+
+def fork_join_layers(layers):
+    """Layers (or "data") whose output is read by a layer of the other kind (chain <-> side branch)."""
+    return {s_ for l in layers for s_ in l.srcs if (l.name in SIDE_BRANCH) != (s_ in SIDE_BRANCH)}
+
+
+class Source(NamedTuple):
+    """What a layer loads: a raw (V,H,W,C) tensor and what normalises it on the load -- the producer's GroupNorm sums, gamma,
+    beta and whether ReLU follows; all None / 0 for the image and for the gradients of the backward pass."""
+    tensor: torch.Tensor
+    stats: Optional[torch.Tensor] = None
+    gamma: Optional[torch.Tensor] = None
+    beta: Optional[torch.Tensor] = None
+    relu: int = 0
+
+
+_NO_SOURCE = Source(None)
+
+
+def launch_layer(lib, l, sources, w_raw, w_prepared, V, h, w, y, stats_out, st):
+    """One layer `l` over V inputs of h x w on the stream handle `st`: `sources` one Source per entry of l.srcs, `w_prepared`
+    the kernel in the layout the kernel reads (transposed layers: or None, then `w_raw` in the TensorFlow layout is
+    gathered), `y` the raw output, `stats_out` its GroupNorm slot sums (None: not wanted)."""
+    p, a = _lib.ptr, sources[0]
+    if l.kind == "dg":
+        _lib.check(lib.mvs_deconv2d_gn_f32(p(a.tensor), p(a.stats), p(a.gamma), p(a.beta), l.cins[0], a.relu, p(w_raw), p(w_prepared),
+                                           V, h, w, l.cout, p(y), p(stats_out), st), "mvs_deconv2d_gn_f32")
+    else:
+        b, c2 = (sources[1], l.cins[1]) if len(sources) > 1 else (_NO_SOURCE, 0)
+        _lib.check(lib.mvs_conv2d_gn_f32(p(a.tensor), p(a.stats), p(a.gamma), p(a.beta), l.cins[0], a.relu,
+                                         p(b.tensor), p(b.stats), p(b.gamma), p(b.beta), c2, b.relu,
+                                         p(w_prepared), V, h, w, l.cout, l.k, l.stride, p(y), p(stats_out), st), "mvs_conv2d_gn_f32")
+
+
+class LayerWeights(NamedTuple):
+    prepared: Optional[torch.Tensor]                       # None: a transposed layer the library runs on the raw kernel
+    raw: Optional[torch.Tensor]                            # transposed layers only
+    gamma: Optional[torch.Tensor]
+    beta: Optional[torch.Tensor]
+
+
+class _Step(NamedTuple):
+    """One layer of a pass: what launch_layer takes besides the sources and the stream."""
+    layer: TowerLayer
+    weights: LayerWeights
+    h: int
+    w: int
+    y: torch.Tensor
+    stats_out: Optional[torch.Tensor]
+
+
+class _Pass(NamedTuple):
+    """The leading V views of a set of buffers."""
+    data: torch.Tensor                                     # (V,H,W,4): the image padded 3 -> 4 channels (channel 3 stays 0)
+    steps: list                                            # one _Step per layer; the last one's y is the features
+
+
+class _Buffers(NamedTuple):
+    capacity: int                                          # views the tensors below are sized for
+    acts: dict                                             # layer -> raw output (capacity, ho, wo, cout)
+    stat_offsets: dict                                     # layer -> start of its slot sums in `stats`
+    stats: torch.Tensor                                    # float64 slab of every layer's GroupNorm slot sums
+    data: torch.Tensor
+    csum: torch.Tensor                                     # workspace of mvs_center_images_u8_f32
+    sizes: list                                            # feature_net.layer_sizes of the image size
+    passes: dict                                           # V -> _Pass
 
 
 class HipUNetDS2GN:
@@ -39,76 +111,69 @@ class HipUNetDS2GN:
         self.device = torch.device(device)
         self.side_streams = side_streams if side_streams == "auto" else int(side_streams)
         self._streams = None
-        self._choice = {}                                  # (V, H, W) -> list of side streams (possibly empty)
-        # layers whose output is read by a layer of the other kind (chain <-> side branch)
-        self._fork_join = {s_ for name, _k, srcs, *_r in UNET_LAYERS for s_ in srcs if (name in SIDE_BRANCH) != (s_ in SIDE_BRANCH)}
+        self._choice = {}                                  # (H, W) -> list of side streams (possibly empty)
+        self.table = table = tower_layers_of({name: np.asarray(p["w"]) for name, p in params.items()})
+        self._fork_join = fork_join_layers(table)
         lib = _lib.load()
         self.slots = lib.mvs_gn_stat_slots()               # partial GroupNorm accumulators per (view, group)
-        chans = {"data": 4}                               # the image is padded 3 -> 4 channels
-        self.layers = []
-        for name, kind, srcs, k, _mult, stride in UNET_LAYERS:
-            p = params[name]
-            w = np.asarray(p["w"], np.float32)
-            cins = [chans[s] for s in srcs]
-            wraw = None
-            if kind == "dg":
-                cout = w.shape[2]
-                wraw = torch.as_tensor(w).contiguous().to(self.device)
-                n = lib.mvs_deconv2d_prepared_floats(cins[0], cout)
-                wd = None
-                if n:                                      # MFMA path; otherwise the VALU gather on the raw weights
-                    wd = torch.empty(n, dtype=torch.float32, device=self.device)
-                    _lib.check(lib.mvs_deconv2d_prepare_f32(_lib.ptr(wraw), cins[0], cout, _lib.ptr(wd), _lib.stream_ptr()),
-                               "mvs_deconv2d_prepare_f32")
-            else:
-                cout = w.shape[3]
-                if srcs == ("data",):                     # zero weights for the padding channel
-                    w = np.concatenate([w, np.zeros(w.shape[:2] + (1, cout), np.float32)], axis=2)
-                c1, c2 = cins[0], (cins[1] if len(cins) > 1 else 0)
-                n = lib.mvs_conv2d_prepared_floats(k, c1, c2, cout)
-                wd = torch.empty(n, dtype=torch.float32, device=self.device)
-                wt = torch.as_tensor(w).contiguous().to(self.device)
-                _lib.check(lib.mvs_conv2d_prepare_f32(_lib.ptr(wt), k, c1, c2, cout, _lib.ptr(wd), _lib.stream_ptr()),
-                           "mvs_conv2d_prepare_f32")
-            g = b = None
-            if kind != "c":
-                g = torch.as_tensor(np.asarray(p["gamma"], np.float32)).to(self.device)
-                b = torch.as_tensor(np.asarray(p["beta"], np.float32)).to(self.device)
-            chans[name] = cout
-            self.layers.append((name, kind, srcs, k, stride, wd, g, b, cins, cout, wraw))
+        self.layers = [(l, self._upload(lib, l, params[l.name])) for l in table]
         torch.cuda.synchronize(self.device)
-        self.out_channels = self.layers[-1][9]
+        self.out_channels = table[-1].cout
         self._bufs, self._retired = {}, []
+
+    def _upload(self, lib, l, p):
+        """One layer's variables on the device, the kernel laid out for mvs_conv2d_gn_f32 / mvs_deconv2d_gn_f32."""
+        w = np.asarray(p["w"], np.float32)
+        wraw = wd = None
+        if l.kind == "dg":
+            wraw = torch.as_tensor(w).contiguous().to(self.device)
+            n = lib.mvs_deconv2d_prepared_floats(l.cins[0], l.cout)
+            if n:                                          # MFMA path; otherwise the VALU gather on the raw weights
+                wd = torch.empty(n, dtype=torch.float32, device=self.device)
+                _lib.check(lib.mvs_deconv2d_prepare_f32(_lib.ptr(wraw), l.cins[0], l.cout, _lib.ptr(wd), _lib.stream_ptr()),
+                           "mvs_deconv2d_prepare_f32")
+        else:
+            if l.srcs == ("data",):                        # zero weights for the padding channel
+                w = np.concatenate([w, np.zeros(w.shape[:2] + (1, l.cout), np.float32)], axis=2)
+            c1, c2 = l.cins[0], (l.cins[1] if len(l.cins) > 1 else 0)
+            wd = torch.empty(lib.mvs_conv2d_prepared_floats(l.k, c1, c2, l.cout), dtype=torch.float32, device=self.device)
+            wt = torch.as_tensor(w).contiguous().to(self.device)
+            _lib.check(lib.mvs_conv2d_prepare_f32(_lib.ptr(wt), l.k, c1, c2, l.cout, _lib.ptr(wd), _lib.stream_ptr()),
+                       "mvs_conv2d_prepare_f32")
+        g = b = None
+        if l.kind != "c":
+            g = torch.as_tensor(np.asarray(p["gamma"], np.float32)).to(self.device)
+            b = torch.as_tensor(np.asarray(p["beta"], np.float32)).to(self.device)
+        return LayerWeights(wd, wraw, g, b)
 
     def _plan(self, V, H, W, slot=0):
         """Activation buffers and one float64 slab of GroupNorm sums for a (V, H, W) input (`slot`: independent sets of buffers
-        for passes that run concurrently on different streams).  One set per image size, sized for the largest V seen so far:
-        a smaller batch uses the leading V views of every buffer (V is the outermost dimension of all of them), so a session
-        whose groups bring 1 .. 16 new images allocates once or twice, not once per distinct V."""
+        for passes that run concurrently on different streams) -> the set and its _Pass for V.  One set per image size, sized
+        for the largest V seen so far: a smaller batch uses the leading V views of every buffer (V is the outermost dimension
+        of all of them), so a session whose groups bring 1 .. 16 new images allocates once or twice, not once per distinct V."""
         key = (H, W, slot)
         held = self._bufs.get(key)
-        if held is None or held[0] < V:
-            shapes = {"data": (H, W)}
+        if held is None or held.capacity < V:
+            sizes = layer_sizes(self.table, H, W)
             acts, offs, total = {}, {}, 0
-            for name, kind, srcs, k, stride, _w, _g, _b, _cins, cout, _wr in self.layers:
-                h, w = shapes[srcs[0]]
-                ho, wo = (2 * h, 2 * w) if kind == "dg" else (-(-h // stride), -(-w // stride))
-                shapes[name] = (ho, wo)
-                acts[name] = torch.empty((V, ho, wo, cout), dtype=torch.float32, device=self.device)
-                offs[name] = total
-                total += V * (cout // 8) * 2 * self.slots
+            for l, (_h, _w, ho, wo) in zip(self.table, sizes):
+                acts[l.name] = torch.empty((V, ho, wo, l.cout), dtype=torch.float32, device=self.device)
+                offs[l.name] = total
+                total += V * (l.cout // 8) * 2 * self.slots
             stats = torch.zeros(total, dtype=torch.float64, device=self.device)
-            data = torch.zeros((V, H, W, 4), dtype=torch.float32, device=self.device)  # the image padded 3 -> 4 channels (channel 3 stays 0)
+            data = torch.zeros((V, H, W, 4), dtype=torch.float32, device=self.device)
             csum = torch.empty(_lib.load().mvs_center_images_workspace_bytes(V) // 8, dtype=torch.int64, device=self.device)
             if held is not None:                            # a pass on another stream may still be reading the smaller set: keep it
                 self._retired.append(held)
-            held = self._bufs[key] = (V, acts, offs, stats, shapes, data, {}, csum)
-        cap, acts, offs, stats, shapes, data, views, csum = held
-        if cap != V:
-            if V not in views:
-                views[V] = ({n_: a[:V] for n_, a in acts.items()}, data[:V])
-            acts, data = views[V]
-        return acts, offs, stats, shapes, data, csum
+            held = self._bufs[key] = _Buffers(V, acts, offs, stats, data, csum, sizes, {})
+        if V not in held.passes:
+            steps = []
+            for (l, wt), (h, w, _ho, _wo) in zip(self.layers, held.sizes):
+                o = held.stat_offsets[l.name]
+                so = held.stats[o:o + V * (l.cout // 8) * 2 * self.slots] if l.kind != "c" else None
+                steps.append(_Step(l, wt, h, w, held.acts[l.name][:V], so))
+            held.passes[V] = _Pass(held.data[:V], steps)
+        return held, held.passes[V]
 
     def _side_streams_for(self, x):
         """The side streams of this input shape (see the class docstring)."""
@@ -153,48 +218,31 @@ class HipUNetDS2GN:
     def _run(self, x, side, slot=0):
         lib = _lib.load()
         V, H, W, _ = x.shape
-        acts, offs, stats, shapes, data, csum = self._plan(V, H, W, slot)
-        stats.zero_()
+        bufs, this = self._plan(V, H, W, slot)
+        bufs.stats.zero_()
         if x.dtype == torch.uint8:
             x = x.contiguous()
-            _lib.check(lib.mvs_center_images_u8_f32(_lib.ptr(x), V, H, W, _lib.ptr(data), _lib.ptr(csum), _lib.stream_ptr()),
+            _lib.check(lib.mvs_center_images_u8_f32(_lib.ptr(x), V, H, W, _lib.ptr(this.data), _lib.ptr(bufs.csum), _lib.stream_ptr()),
                        "mvs_center_images_u8_f32")
         else:
-            data[..., :3] = x
+            this.data[..., :3] = x
         main = torch.cuda.current_stream(self.device)
         ns = len(side)
-        stream_of = lambda name: (side[SIDE_BRANCH[name] % ns] if ns and name in SIDE_BRANCH else main)
-        done = {}                                          # layer -> event, for layers read from another stream
-        if ns:
-            done["data"] = main.record_event()
-        src_of = {"data": (data, None, None, None, 0)}    # tensor, stats view, gamma, beta, relu
+        done = {"data": main.record_event()} if ns else {}     # layer -> event, for layers read from another stream
+        src_of = {"data": Source(this.data)}
         where = {"data": main}
-        for name, kind, srcs, k, stride, wd, g, b, cins, cout, wraw in self.layers:
-            h, w = shapes[srcs[0]]
-            y = acts[name]
-            so = stats[offs[name]:offs[name] + V * (cout // 8) * 2 * self.slots] if kind != "c" else None
-            a = src_of[srcs[0]]
-            st_ = stream_of(name)
-            for s_ in srcs:                                # producers on another stream: wait for their event
+        for l, wt, h, w, y, so in this.steps:
+            name = l.name
+            st_ = side[SIDE_BRANCH[name] % ns] if ns and name in SIDE_BRANCH else main
+            for s_ in l.srcs:                              # producers on another stream: wait for their event
                 if where[s_] is not st_:
                     if s_ not in done:
                         done[s_] = where[s_].record_event()
                     st_.wait_event(done[s_])
-            st = C.c_void_p(st_.cuda_stream)
-            if kind == "dg":
-                _lib.check(lib.mvs_deconv2d_gn_f32(_lib.ptr(a[0]), _lib.ptr(a[1]), _lib.ptr(a[2]), _lib.ptr(a[3]), cins[0], a[4],
-                                                   _lib.ptr(wraw), _lib.ptr(wd), V, h, w, cout, _lib.ptr(y), _lib.ptr(so), st),
-                           "mvs_deconv2d_gn_f32")
-            else:
-                bsrc = src_of[srcs[1]] if len(srcs) > 1 else (None, None, None, None, 0)
-                _lib.check(lib.mvs_conv2d_gn_f32(_lib.ptr(a[0]), _lib.ptr(a[1]), _lib.ptr(a[2]), _lib.ptr(a[3]), cins[0], a[4],
-                                                 _lib.ptr(bsrc[0]), _lib.ptr(bsrc[1]), _lib.ptr(bsrc[2]), _lib.ptr(bsrc[3]),
-                                                 cins[1] if len(cins) > 1 else 0, bsrc[4],
-                                                 _lib.ptr(wd), V, h, w, cout, k, stride, _lib.ptr(y), _lib.ptr(so), st),
-                           "mvs_conv2d_gn_f32")
+            launch_layer(lib, l, [src_of[s_] for s_ in l.srcs], wt.raw, wt.prepared, V, h, w, y, so, C.c_void_p(st_.cuda_stream))
             # consumers apply this layer's GroupNorm: ReLU after conv_gn, none after deconv_gn (network.py:357)
-            src_of[name] = (y, so, g, b, 1 if kind == "cg" else 0)
+            src_of[name] = Source(y, so, wt.gamma, wt.beta, l.relu)
             where[name] = st_
             if ns and name in self._fork_join:             # read from another stream later: its event is recorded right behind it
                 done[name] = st_.record_event()
-        return acts["conv10_2"].clone()
+        return this.steps[-1].y.clone()

@@ -127,6 +127,24 @@ def test_hip_towers_match_float64_autograd(size, hooks, into, lib_built):
     assert not bad, (bound, bad)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.uint8])
+@pytest.mark.parametrize("size", [(2, 32, 48), (3, 48, 80)])
+def test_training_forward_is_the_inference_forward(size, dtype, lib_built):
+    """`hip_towers` and `HipUNetDS2GN` launch their layers through one function (feature_net_hip.launch_layer): the same
+    launches, another order of the float64 GroupNorm atomics -- the 1e-6 tests/test_gpu_unet.py holds two such passes to."""
+    from mvsnet_amd.feature_net_hip import HipUNetDS2GN
+    from mvsnet_amd.feature_net_train import hip_towers
+    images, params, _g = tower_problem(*size)
+    img = t(images)
+    if dtype == torch.uint8:
+        img = torch.randint(0, 256, img.shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(size[2])).to(DEV)
+    got = n(hip_towers(img, {name: {key: t(v) for key, v in d.items()} for name, d in params.items()}))
+    want = n(HipUNetDS2GN(params, DEV, side_streams=0)(img))
+    dist = np.abs(got - want).max() / np.abs(want).max()
+    print("\n%s %s: max |training - inference| / max |inference| = %.3e" % (size, dtype, dist))
+    assert got.shape == want.shape == (size[0], size[1] // 4, size[2] // 4, 32) and dist < 1e-6, dist
+
+
 def test_weight_plan_jobs_are_the_cases_of_this_file(lib_built):
     """What `_WeightPlan` really prepares for the backward on this device = the case lists above."""
     from mvsnet_amd.feature_net import UNET_LAYERS
