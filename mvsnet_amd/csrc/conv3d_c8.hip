@@ -63,7 +63,7 @@ struct FuseArgs {
     double* stats2;       // (2,16) float64 sums or null
     // The 240 workgroups of a metric-size launch (one per CU) all finish together: their float64 atomics on the 48
     // sum addresses serialised into a ~19 us tail.  With slots they go to (slots, 2, C) partial rows that the
-    // consumers' bn_affine4 adds up (regnet.hip: 8 rows for 3dconv0_1, 4 for 3dconv1_0 -- what fits the layer's
+    // consumers' fold (conv_common.h: bn_sum1) adds up (regnet.hip: 8 rows for 3dconv0_1, 4 for 3dconv1_0 -- what fits the layer's
     // 128-double statistics slab).
     int slots1, slots2;
     // SPAN schedule (conv3d_c8_kernel<.., SPAN = true>): groups of `span_g` tiles are cut into `span_m` plane ranges over the
@@ -125,7 +125,11 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
     const int c4 = tid % CQ;
     float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
     if (AFF && a.xs) { sc = *(const float4*)(a.xs + 4 * c4); sh = *(const float4*)(a.xb + 4 * c4); }
-    else if (AFF && a.bn.stats) bn_affine4(a.bn, 4 * c4, sc, sh);
+    if (AFF) {                                    // producer given as raw sums: folded once per workgroup (conv_common.h)
+        __shared__ __attribute__((aligned(16))) float bn_tab[2 * CIN];
+        float4 sc2, sh2;
+        bn_affine4_wg(a.bn, !a.xs, a.bn, false, bn_tab, 4 * c4, sc, sh, sc2, sh2);
+    }
 
     float4 pre[NIT];
     int goff[NIT], loff[NIT];

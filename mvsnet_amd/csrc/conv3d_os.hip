@@ -95,9 +95,12 @@ __device__ __forceinline__ void os_block(const ConvArgs& a, int nbh, int nbw, in
     };
     // the producers' float64 BatchNorm sums first: they come from memory-side atomics (an L2 miss) and head the longest
     // dependent chain of the prologue (sums -> float64 scale / shift -> staged values -> LDS -> barrier)
-    BnSums4 bs1 = {}, bs2 = {};
-    if (!a.xs && a.bn.stats) bs1 = bn_sums4(a.bn, 4 * (tid % CQ));
-    if (HAS_X2 && !a.x2s && a.bn2.stats) bs2 = bn_sums4(a.bn2, 4 * (tid % CQ));
+    // -- one thread per channel (conv_common.h: threads 0.. the first producer's, threads 128.. the second's)
+    __shared__ __attribute__((aligned(16))) float bn_tab[4 * CIN];
+    const bool fold1 = !a.xs && a.bn.stats, fold2 = HAS_X2 && !a.x2s && a.bn2.stats;
+    BnSum1 bs1 = {}, bs2 = {};
+    if (fold1) bs1 = bn_sum1(a.bn, 0);
+    if (fold2) bs2 = bn_sum1(a.bn2, 128);
     float4 areg[PF];
 #pragma unroll
     for (int s = 0; s < PF; ++s) areg[s] = load_a(s);       // in flight under the staging below
@@ -123,15 +126,20 @@ __device__ __forceinline__ void os_block(const ConvArgs& a, int nbh, int nbw, in
             if (HAS_X2) v2[i] = __builtin_amdgcn_raw_buffer_load_b128(x2r, off, 0, 0);
             ok_mask |= ok ? (1u << i) : 0u;
         }
-        // the producers' BatchNorm (float64 sums -> scale, shift) while the loads above are in flight
+        // the producers' BatchNorm (float64 sums -> scale, shift -> LDS, once per workgroup) while the loads above are in flight
         float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
         float4 sc2 = sc, sh2 = sh;
         const bool aff = a.xs != nullptr || a.bn.stats != nullptr;
-        if (a.xs) { sc = *(const float4*)(a.xs + 4 * c4); sh = *(const float4*)(a.xb + 4 * c4); }
-        else if (a.bn.stats) bn_affine4_from(a.bn, bs1, sc, sh);
         const bool aff2 = HAS_X2 && (a.x2s != nullptr || a.bn2.stats != nullptr);
+        if (a.xs) { sc = *(const float4*)(a.xs + 4 * c4); sh = *(const float4*)(a.xb + 4 * c4); }
         if (HAS_X2 && a.x2s) { sc2 = *(const float4*)(a.x2s + 4 * c4); sh2 = *(const float4*)(a.x2b + 4 * c4); }
-        else if (HAS_X2 && a.bn2.stats) bn_affine4_from(a.bn2, bs2, sc2, sh2);
+        if (fold1 || fold2) {                                // workgroup-uniform
+            if (fold1) bn_fold_store(a.bn, bs1, 0, bn_tab);
+            if (fold2) bn_fold_store(a.bn2, bs2, 128, bn_tab + 2 * CIN);
+            __syncthreads();
+            if (fold1) bn_affine4_lds(bn_tab, a.bn.C, 4 * c4, sc, sh);
+            if (fold2) bn_affine4_lds(bn_tab + 2 * CIN, a.bn2.C, 4 * c4, sc2, sh2);
+        }
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
             const int f = tid + 256 * i;

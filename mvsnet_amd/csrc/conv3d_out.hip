@@ -7,7 +7,11 @@
 // march as the MFMA kernels -- a workgroup owns an 8 x 32 (h x w) column, stages each normalised
 // input plane once in LDS (12-float positions: conflict-free 16-B reads for consecutive lanes) and
 // each thread adds the plane's 9 in-plane taps into the three output planes q+1, q, q-1.
-// Roofline: HBM, 2*Cin*4 + 4 bytes per voxel.
+// Roofline: HBM, 2*Cin*4 + 4 bytes per voxel: 297 MB in 66.5 us = 4.5 TB/s at the metric workload.  Not bound by how far ahead a
+// workgroup requests its planes: with the raw planes two ahead in an LDS ring filled by global_load_lds (two workgroups per CU,
+// counted vmcnt, bare s_barrier; bit-identical) the layer took 67.8 us against 66.7, and at no chunk length from 4 to 48 planes
+// was the depth map rate above this kernel's (profiles/r07_conv3d_out_lds_ring.patch, EXPERIMENTS.md round 7); a second register
+// set had measured 72.0 against 67.9 us before.
 #include "conv_common.h"
 
 namespace {
@@ -52,10 +56,13 @@ conv3d_out_kernel(ConvArgs a) {
     const bool has_x2 = a.x2 != nullptr;
     const bool has_aff = a.xs != nullptr || a.bn.stats != nullptr;
     if (a.xs) { sc = *(const float4*)(a.xs + 4 * c4); sh = *(const float4*)(a.xb + 4 * c4); }
-    else if (a.bn.stats) bn_affine4(a.bn, 4 * c4, sc, sh);
     const bool has_aff2 = has_x2 && (a.x2s != nullptr || a.bn2.stats != nullptr);
     if (has_x2 && a.x2s) { sc2 = *(const float4*)(a.x2s + 4 * c4); sh2 = *(const float4*)(a.x2b + 4 * c4); }
-    else if (has_x2 && a.bn2.stats) bn_affine4(a.bn2, 4 * c4, sc2, sh2);
+    // producers given as raw sums: folded once per workgroup (conv_common.h).  The table borrows slab[1], which is first written
+    // after the barrier below the first write_slab -- LDS of its own would cost Cin = 16 its third workgroup per CU.
+    float* bn_tab = slab[1];
+    static_assert(NPOS * S >= 4 * CIN, "the BatchNorm table fits a slab");
+    bn_affine4_wg(a.bn, !a.xs, a.bn2, has_x2 && !a.x2s, bn_tab, 4 * c4, sc, sh, sc2, sh2);
 
     float4 pre[NIT], pre2[NIT];
     // Per-thread staging map, identical for every plane: element offset inside one input plane
@@ -160,6 +167,7 @@ int launch_out(const ConvArgs& a0, hipStream_t st) {
     ConvArgs a = a0;
     const int tiles = ((a.H + OTH - 1) / OTH) * ((a.W + OTW - 1) / OTW);
     a.planes_per_wg = conv_pick_planes(a.D, tiles, 2, 768);
+    if (const int hk = mvs_hook(MVS_HOOK_OUT_PLANES)) a.planes_per_wg = hk < a.D ? hk : a.D;      // tests, measurements
     dim3 grid(tiles, 1, (a.D + a.planes_per_wg - 1) / a.planes_per_wg);
     conv3d_out_kernel<CIN><<<grid, 256, 0, st>>>(a);
     return (int)hipGetLastError();

@@ -75,10 +75,11 @@ conv3d_s2_kernel(ConvArgs a) {
     float4 sc2 = sc, sh2 = sh;
     const bool has_aff = a.xs != nullptr || a.bn.stats != nullptr;
     if (a.xs) { sc = *(const float4*)(a.xs + 4 * c4); sh = *(const float4*)(a.xb + 4 * c4); }
-    else if (a.bn.stats) bn_affine4(a.bn, 4 * c4, sc, sh);
     const bool has_aff2 = HAS_X2 && (a.x2s != nullptr || a.bn2.stats != nullptr);
     if (HAS_X2 && a.x2s) { sc2 = *(const float4*)(a.x2s + 4 * c4); sh2 = *(const float4*)(a.x2b + 4 * c4); }
-    else if (HAS_X2 && a.bn2.stats) bn_affine4(a.bn2, 4 * c4, sc2, sh2);
+    // producers given as raw sums: folded once per workgroup (conv_common.h)
+    __shared__ __attribute__((aligned(16))) float bn_tab[4 * CIN];
+    bn_affine4_wg(a.bn, !a.xs, a.bn2, HAS_X2 && !a.x2s, bn_tab, 4 * c4, sc, sh, sc2, sh2);
     const float lo = has_aff ? 0.f : -INFINITY, lo2 = has_aff2 ? 0.f : -INFINITY;   // ReLU floor (or identity)
 
     float4 pre[NIT];

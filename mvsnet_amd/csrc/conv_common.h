@@ -29,39 +29,57 @@ __device__ __forceinline__ void bn_affine_finish(double s1, double s2, double in
     shift = beta - (float)mean * inv;
 }
 
-__device__ __forceinline__ void bn_affine4(const BnSrc& b, int c0, float4& sc, float4& sh) {
-    float s[4], t[4];
-    const double ic = 1.0 / b.count;
+// Once per workgroup instead of once per thread: thread t0 + c (c < C) folds channel c -- the nslot partial rows added in row
+// order 0 .. nslot - 1, then bn_affine_finish: for equal sums the (scale, shift) bits do not depend on who folds -- and
+// leaves scale in tab[c], shift in tab[C + c] (2 * C floats of LDS).  After a barrier every thread takes its channel quad with
+// bn_affine4_lds.  All rows are requested before the first is added (rows past nslot re-read row 0 and are not added): a row
+// then costs a load, not a round trip to L2.  Two halves for kernels that want the sums in flight early: bn_sum1 loads,
+// bn_fold_store finishes and stores.
+constexpr int MVS_BN_SLOTS_MAX = 8;      // partial rows per BatchNorm layer in the regulariser's workspace
+struct BnSum1 { double s1, s2; float g, b; bool mine; };
+__device__ __forceinline__ BnSum1 bn_sum1(const BnSrc& b, int t0) {
+    BnSum1 r = {0.0, 0.0, 0.f, 0.f, false};
+    const int c = (int)threadIdx.x - t0;
+    if (c < 0 || c >= b.C) return r;
+    double p1[MVS_BN_SLOTS_MAX], p2[MVS_BN_SLOTS_MAX];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        double s1 = b.stats[c0 + k], s2 = b.stats[b.C + c0 + k];
-        for (int sl = 1; sl < b.nslot; ++sl) { s1 += b.stats[sl * 2 * b.C + c0 + k]; s2 += b.stats[sl * 2 * b.C + b.C + c0 + k]; }
-        bn_affine_finish(s1, s2, ic, b.gamma[c0 + k], b.beta[c0 + k], b.eps, s[k], t[k]);
+    for (int sl = 0; sl < MVS_BN_SLOTS_MAX; ++sl) {
+        const int row = sl < b.nslot ? sl : 0;
+        p1[sl] = b.stats[row * 2 * b.C + c]; p2[sl] = b.stats[row * 2 * b.C + b.C + c];
     }
-    sc = make_float4(s[0], s[1], s[2], s[3]);
-    sh = make_float4(t[0], t[1], t[2], t[3]);
-}
-
-// The same in two halves, for kernels that want the float64 sums in flight early: bn_sums4 only loads (and adds the partial
-// rows), bn_affine4_from turns the sums into (scale, shift).
-struct BnSums4 { double s1[4], s2[4]; float g[4], b[4]; };
-__device__ __forceinline__ BnSums4 bn_sums4(const BnSrc& b, int c0) {
-    BnSums4 r;
+    r.s1 = p1[0]; r.s2 = p2[0];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        double s1 = b.stats[c0 + k], s2 = b.stats[b.C + c0 + k];
-        for (int sl = 1; sl < b.nslot; ++sl) { s1 += b.stats[sl * 2 * b.C + c0 + k]; s2 += b.stats[sl * 2 * b.C + b.C + c0 + k]; }
-        r.s1[k] = s1; r.s2[k] = s2; r.g[k] = b.gamma[c0 + k]; r.b[k] = b.beta[c0 + k];
-    }
+    for (int sl = 1; sl < MVS_BN_SLOTS_MAX; ++sl)
+        if (sl < b.nslot) { r.s1 += p1[sl]; r.s2 += p2[sl]; }
+    r.g = b.gamma[c]; r.b = b.beta[c]; r.mine = true;
     return r;
 }
-__device__ __forceinline__ void bn_affine4_from(const BnSrc& b, const BnSums4& r, float4& sc, float4& sh) {
-    float s[4], t[4];
-    const double ic = 1.0 / b.count;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) bn_affine_finish(r.s1[k], r.s2[k], ic, r.g[k], r.b[k], b.eps, s[k], t[k]);
-    sc = make_float4(s[0], s[1], s[2], s[3]);
-    sh = make_float4(t[0], t[1], t[2], t[3]);
+__device__ __forceinline__ void bn_fold_store(const BnSrc& b, const BnSum1& r, int t0, float* tab) {
+    if (!r.mine) return;
+    const int c = (int)threadIdx.x - t0;
+    float s, t;
+    bn_affine_finish(r.s1, r.s2, 1.0 / b.count, r.g, r.b, b.eps, s, t);
+    tab[c] = s; tab[b.C + c] = t;
+}
+__device__ __forceinline__ void bn_fold_to_lds(const BnSrc& b, int t0, float* tab) { bn_fold_store(b, bn_sum1(b, t0), t0, tab); }
+__device__ __forceinline__ void bn_affine4_lds(const float* tab, int C, int c0, float4& sc, float4& sh) {
+    sc = *(const float4*)(tab + c0);
+    sh = *(const float4*)(tab + C + c0);
+}
+// A prologue's whole step for one or two producers given as raw sums (threads 0.. fold `b1`, threads 128.. fold `b2`: 128 is
+// the widest layer; use1 / use2: that producer is not given as a finalised affine): fold, barrier, read.  `tab` holds 2 * C
+// floats per producer, 16-byte aligned.  Every thread of the workgroup must call it (it holds a barrier); producers without
+// stats leave their (sc, sh) untouched.
+__device__ __forceinline__ void bn_affine4_wg(const BnSrc& b1, bool use1, const BnSrc& b2, bool use2, float* tab, int c0,
+                                              float4& sc, float4& sh, float4& sc2, float4& sh2) {
+    const bool f1 = use1 && b1.stats, f2 = use2 && b2.stats;
+    if (!f1 && !f2) return;                                       // workgroup-uniform
+    float* tab2 = tab + (f1 ? 2 * b1.C : 0);
+    if (f1) bn_fold_to_lds(b1, 0, tab);
+    if (f2) bn_fold_to_lds(b2, 128, tab2);
+    __syncthreads();
+    if (f1) bn_affine4_lds(tab, b1.C, c0, sc, sh);
+    if (f2) bn_affine4_lds(tab2, b2.C, c0, sc2, sh2);
 }
 
 // A kernel argument: the order, types and size of the fields are fixed.  Every field defaults to null / 0; the host builds one
@@ -88,8 +106,8 @@ static inline ConvArgs conv_args(const float* x, const float* w, float* y, doubl
 // BatchNorm sums go to memory-side float64 atomics.  With every workgroup of a layer adding into the same 2*C doubles the
 // atomics cost ~5 us at the end of each 240..960-workgroup layer (measured by leaving them out: the low-resolution chain
 // went 140 -> 120 us; they are native global_atomic_add_f64, one instruction of 32..128 lanes per workgroup).  A layer's sums
-// can be spread over `stats_slots` partial rows, workgroup w adds into row w % slots, and the consumer's bn_affine4 /
-// bn_sums4 add the rows up (BnSrc::nslot); regnet.hip uses 2 rows (more rows cost the consumers more than they save).
+// can be spread over `stats_slots` partial rows, workgroup w adds into row w % slots, and the consumer's fold (bn_sum1) adds
+// the rows up (BnSrc::nslot); the row counts and what they measured are in regnet.hip.
 __device__ __forceinline__ double* conv_stats_row(const ConvArgs& a) {
     const int slots = a.stats_slots > 1 ? a.stats_slots : 1;
     return a.stats + (size_t)((blockIdx.x + gridDim.x * blockIdx.z) % slots) * 2 * a.cout_total;
@@ -197,7 +215,6 @@ __device__ __forceinline__ void load_prepared_weights(float* wl, const float* wp
 }
 
 // launchers implemented in the kernel files; MVS_E_SHAPE when the shape is outside their tiling
-constexpr int MVS_BN_SLOTS_MAX = 8;      // partial rows per BatchNorm layer in the regulariser's workspace
 // stride 1 / 2 by (Cin, Cout, stride): picks the MFMA kernel (conv3d_mfma.hip) and sets the stride-2 pads in `a`
 int mvs_conv3d_dispatch(ConvArgs& a, int Cin, int Cout, int stride, hipStream_t st);
 // 3dconv1_1 (a: 16 -> 16, stride 1) and 3dconv2_0 (-> y2, 16 -> 32, stride 2; its sums take a.stats_slots rows too) over the same

@@ -186,14 +186,26 @@ __global__ void bn_fold_rows_kernel(double* stats, int nslot, int n) {
 }
 
 // partial rows per layer: only where EVERY layer has an MFMA kernel (the scalar fallback finalises one row)
-// MVS_BN_SLOTS = 1 / 2 / 4 / 8 measured 858 / 864 / 860 / 848 depth maps/s at the metric workload: more rows shorten the
-// producers' atomic tails but every consumer thread adds the rows up again
-constexpr int BN_SLOTS = 2;
+// More rows shorten the producers' tails of same-address float64 atomics; a consumer workgroup folds the rows once (conv_common.h,
+// bn_sum1: one thread per channel, every row requested before the first is added).  Depth maps/s at the metric workload:
+//   BN_SLOTS                          1       2       4       8
+//   every consumer thread folds     858     864     860     848     (round 2: each row cost the consumers ~3 us per depth map)
+//   one fold per workgroup          945.6   958.8   961.8   969.1   (one run each, PAIR_SLOTS = 2; the parent build 954.0 .. 954.9)
+//   same, medians of three            --      --    984.0   986.3   (another machine: the parent build 967.7 .. 969.7)
+// (MVS_HOOK_BN_SLOTS; profiles/r07_tail_ab.txt).  8 is the workspace's row count, MVS_BN_SLOTS_MAX.
+constexpr int BN_SLOTS = 8;
 // the fused pass over the cost volume spreads its sums over partial rows too (conv3d_c8.hip, FuseArgs)
-// rows of the fused pair's sums: MVS_PAIR_SLOTS = 8 (round 1) / 4 / 2 / 1 measured 864 / 869 / 869 / 870 depth maps/s -- the
-// consumers (3dconv1_1, 2_0 and the 3 840-workgroup 3dconv6_2) pay for every row they add up
+//   PAIR_SLOTS                        1       2       4       8
+//   every consumer thread folds     870     869     869     864     (round 1 .. 2)
+//   one fold per workgroup          960.2   958.8   957.3   958.2   (one run each, BN_SLOTS = 2)
+//   same at BN_SLOTS = 8, medians     --    986.3   987.1   985.1   (of three; the runs of one setting spread over 1 .. 9)
+// no difference outside the spread: the count stays (240 workgroups finish together and add 48 sums each).
 constexpr int PAIR_SLOTS = 2;
 static_assert(BN_SLOTS <= MVS_BN_SLOTS_MAX && PAIR_SLOTS <= MVS_BN_SLOTS_MAX, "rows beyond the workspace's slab");
+static_assert(MVS_BN_SLOTS_MAX == 8, "mvs_set_test_hook admits 1..8 rows");
+// test / measurement hooks: another row count for one call (tests compare the defaults with one row)
+int bn_slots() { const int hk = mvs_hook(MVS_HOOK_BN_SLOTS); return hk ? hk : BN_SLOTS; }
+int pair_slots() { const int hk = mvs_hook(MVS_HOOK_PAIR_SLOTS); return hk ? hk : PAIR_SLOTS; }
 
 // One call of the regulariser: what the steps below share.
 struct Run {
@@ -206,12 +218,13 @@ struct Run {
     size_t ws_floats1;           // a sample's workspace region (regions are 256-byte aligned)
     bool all_mfma;
     int SL;                      // partial rows of every layer's sums
+    int PS;                      // partial rows of the fused pair's sums
     int lp;                      // per-layer event slot of this call (mvs_profile_layers), or -1
     bool pair_done = false;
     bool finalised[N_BN] = {};
 
     double* st(int i) const { return ws.stats + (size_t)i * MVS_BN_SLOTS_MAX * 2 * CMAX * b; }
-    int nslot_of(int i) const { return (pair_done && (i == L01 || i == L10)) ? PAIR_SLOTS : SL; }
+    int nslot_of(int i) const { return (pair_done && (i == L01 || i == L10)) ? PS : SL; }
     BnSrc bn_of(int i) const {   // producer i's raw BatchNorm sums (i < 0: raw input, no BN)
         if (i < 0) return BnSrc{nullptr, nullptr, nullptr, 1.0, eps, 0, 1};
         return BnSrc{st(i), gammas[i], betas[i], count(i), eps, net.co[i], nslot_of(i)};
@@ -301,7 +314,7 @@ int fused_pair(Run& r) {
         ConvArgs a = conv_args(r.cost + (size_t)bi * r.D * r.H * r.W * r.net.ci[L01], r.weights[L01], r.ws.y[L01] + wo, r.st(L01),
                                r.D, r.H, r.W, r.net.co[L01]);
         a.wprep = r.wprep(L01);
-        rc = mvs_conv3d_c8_s2_launch(a, r.weights[L10], r.ws.y[L10] + wo, r.st(L10), r.hs, PAIR_SLOTS, PAIR_SLOTS);
+        rc = mvs_conv3d_c8_s2_launch(a, r.weights[L10], r.ws.y[L10] + wo, r.st(L10), r.hs, r.PS, r.PS);
         if (rc) return rc == MVS_E_SHAPE ? APART : rc;
     }
     if ((rc = r.mark(L01, 1, r.hs)) || (rc = mvs_prof_dominant.mark(slot, 1, r.hs))) return rc;
@@ -405,7 +418,7 @@ int regnet_run(const float* cost, int batch, int D, int H, int W, int cin, int b
     // (volumes of 2 GB and more leave the 32-bit-offset MFMA kernels for the generic ones: one row there)
     const bool all_mfma = impl != MVS_CONV_IMPL_SCALAR && cin == 32 && base == 8 && (long long)D * H * W * cin * 4 < (1LL << 31);
     Run r{cost, batch, D, H, W, base, weights, prepared, gammas, betas, eps, reg, mvs_stream(stream), impl,
-          net_of(cin, base), ws, ws.bytes / sizeof(float), all_mfma, all_mfma ? BN_SLOTS : 1, mvs_prof_layers.claim()};
+          net_of(cin, base), ws, ws.bytes / sizeof(float), all_mfma, all_mfma ? bn_slots() : 1, pair_slots(), mvs_prof_layers.claim()};
     mvs_prof_layers.commit(r.lp);
 
     SideBranch sb;
