@@ -6,12 +6,16 @@ mvsnet/train.py:428-429).  Here the hot path is one `torch.autograd.Function` wh
 are sequences of C-ABI calls: torch owns memory, the 2D towers (`feature_net.UNetDS2GN`, differentiated by
 torch autograd, as north_star keeps them on PyTorch-ROCm) and the loss expressions (`loss.py`).
 
-Layer bookkeeping of RegNetUS0 (mvsnetworks.py:122-158): every BatchNorm layer keeps its RAW output y,
-its float64 batch sums and the folded affine; consumers apply BN+ReLU on load exactly as in inference.
-Backward per layer:  g_a (gradient w.r.t. the post-ReLU activation, one or two consumers) -> BN+ReLU
-backward (two HBM passes) -> g_y -> weight gradient (MFMA contraction over voxels) and input gradient
-(the forward MFMA kernels: conv stride 2 <-> conv_transpose with the same kernel array, stride 1 with the
-flipped / transposed kernel).
+Layer bookkeeping of RegNetUS0 (mvsnetworks.py:122-158): `regnet_layers.REGNET_LAYERS` is the network as data -- kind,
+channels, producers, BatchNorm -- and both passes are loops over it.  Forward (`regnet_forward_train`, table order; the cost
+volume's two readers in one `conv3d_pair` where that kernel is built): every BatchNorm layer keeps its RAW output y, its
+float64 batch sums and the folded affine; consumers apply BN+ReLU on load exactly as in inference.  Backward
+(`regnet_backward`, REGNET_BACKWARD_ORDER: consumers first) per layer:  the one or two gradients its consumers filed for its
+post-ReLU activation -> BN+ReLU backward (two HBM passes) -> g_y -> the input activation (BN+ReLU of the producers, recomputed
+once per producer set and dropped behind its last reader) -> weight gradient (MFMA contraction over voxels) -> input gradient
+(INPUT_GRAD by kind, on the forward MFMA kernels: conv stride 2 <-> conv_transpose with the same kernel array, stride 1 with
+the flipped / transposed kernel), filed under the producers.  The variables' flat order is REGNET_SLOTS, for parameters and
+gradients alike.  tests/test_regnet_table_host.py runs both loops on CPU float64 stand-ins of the single-op wrappers.
 """
 from __future__ import annotations
 
@@ -21,9 +25,9 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .model import BN_EPSILON, REGNET_ORDER, bn_finalize, conv3d, conv3d_pair, cost_volume
-
-BN_LAYERS = REGNET_ORDER[:-1]
+from .model import BN_EPSILON, bn_finalize, conv3d, conv3d_pair, cost_volume
+from .regnet_layers import (BN_LAYERS, REGNET_BACKWARD_ORDER, REGNET_CONSUMERS, REGNET_LAYER, REGNET_LAYERS, REGNET_ORDER, REGNET_PAIR,
+                            REGNET_SLOTS, S1, S2, UP)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -199,55 +203,59 @@ def deconv_input_grad(g_y, w):
 # RegNetUS0 with saved activations
 # ------------------------------------------------------------------------------------------------
 
+# a layer's input gradient from the gradient of its raw output and its own kernel array, by the layer's kind
+INPUT_GRAD = {S1: conv_s1_input_grad, S2: conv_s2_input_grad, UP: deconv_input_grad}
+# how many layers read the same input activation: it is recomputed once and dropped behind the last of them
+_READERS = {srcs: sum(l.srcs == srcs for l in REGNET_LAYERS) for srcs in {l.srcs for l in REGNET_LAYERS}}
+
+
+def _pieces(slab):
+    """Hands out consecutive pieces of one zeroed slab: one fill for all layers' sums instead of one each."""
+    used = [0]
+
+    def take(n):
+        used[0] += n
+        return slab[used[0] - n:used[0]]
+    return take
+
+
+def _pair_fuses(cost, p):
+    """Whether mvs_conv3d_pair_f32 is built for this volume: both of its readers in one pass over it."""
+    base = REGNET_LAYER[REGNET_PAIR[0]].cout_of(p[REGNET_PAIR[0]]["w"])
+    return cost.shape[3] == 32 and base == 8 and not (cost.shape[0] | cost.shape[1] | cost.shape[2]) & 1
+
+
 def regnet_forward_train(cost, p: Dict[str, Dict[str, torch.Tensor]], sync: Optional[SyncBN] = None):
     """cost (D,H,W,32); p[name] = {'w', 'gamma', 'beta'}.  Returns (reg (D,H,W), saved).  `sync`: cross-replica
     BatchNorm statistics (SyncBN)."""
-    dev = cost.device
     y, st, aff = {}, {}, {}
     world = sync.world if sync is not None else 1
-    # every layer's (2, Cout) float64 BatchNorm sums from ONE zeroed slab (round 6: one fill instead of eleven)
-    slab = torch.zeros(sum(2 * max(v["w"].shape[3], v["w"].shape[4]) for v in p.values()), device=dev, dtype=torch.float64)
-    used = [0]
+    couts = {l.name: l.cout_of(p[l.name]["w"]) for l in REGNET_LAYERS}
+    # every layer's (2, Cout) float64 BatchNorm sums from ONE zeroed slab
+    take = _pieces(torch.zeros(sum(2 * couts[n] for n in BN_LAYERS), device=cost.device, dtype=torch.float64))
+    stats = lambda name: take(2 * couts[name]).view(2, couts[name])
 
-    def zeros2(cout):
-        o = used[0]
-        used[0] += 2 * cout
-        return slab[o:o + 2 * cout].view(2, cout)
-
-    def layer(name, x, stride=1, x_aff=None, skip=None, skip_aff=None, transpose=False):
-        cout = p[name]["w"].shape[3] if transpose else p[name]["w"].shape[4]
-        s = zeros2(cout)
-        out = conv3d(x, p[name]["w"], stride, x_aff, skip, skip_aff, s, transpose)
+    def batch_norm(name, out, s):
         if world > 1:
             sync.all_reduce(s)
         y[name], st[name] = out, s
-        aff[name] = bn_finalize(s, (out.numel() // cout) * world, p[name]["gamma"], p[name]["beta"])
+        aff[name] = bn_finalize(s, (out.numel() // couts[name]) * world, p[name]["gamma"], p[name]["beta"])
 
-    if cost.shape[3] == 32 and p["3dconv0_1"]["w"].shape[4] == 8 and not (cost.shape[0] | cost.shape[1] | cost.shape[2]) & 1:
-        # both consumers of the cost volume in one pass over it (mvs_conv3d_pair_f32)
-        s01, s10 = zeros2(8), zeros2(16)
-        y["3dconv0_1"], y["3dconv1_0"] = conv3d_pair(cost, p["3dconv0_1"]["w"], p["3dconv1_0"]["w"], s01, s10)
-        for nm, s in (("3dconv0_1", s01), ("3dconv1_0", s10)):
-            if world > 1:
-                sync.all_reduce(s)
-            st[nm] = s
-            aff[nm] = bn_finalize(s, (y[nm].numel() // y[nm].shape[3]) * world, p[nm]["gamma"], p[nm]["beta"])
-        fused = True
-    else:
-        fused = False
-        layer("3dconv1_0", cost, 2)
-    layer("3dconv2_0", y["3dconv1_0"], 2, aff["3dconv1_0"])
-    layer("3dconv3_0", y["3dconv2_0"], 2, aff["3dconv2_0"])
-    if not fused:
-        layer("3dconv0_1", cost, 1)
-    layer("3dconv1_1", y["3dconv1_0"], 1, aff["3dconv1_0"])
-    layer("3dconv2_1", y["3dconv2_0"], 1, aff["3dconv2_0"])
-    layer("3dconv3_1", y["3dconv3_0"], 1, aff["3dconv3_0"])
-    layer("3dconv4_0", y["3dconv3_1"], 2, aff["3dconv3_1"], transpose=True)
-    layer("3dconv5_0", y["3dconv4_0"], 2, aff["3dconv4_0"], y["3dconv2_1"], aff["3dconv2_1"], transpose=True)
-    layer("3dconv6_0", y["3dconv5_0"], 2, aff["3dconv5_0"], y["3dconv1_1"], aff["3dconv1_1"], transpose=True)
-    reg = conv3d(y["3dconv6_0"], p["3dconv6_2"]["w"], 1, aff["3dconv6_0"], y["3dconv0_1"], aff["3dconv0_1"])
-    return reg[..., 0], (cost, y, st, aff, sync)
+    fused = _pair_fuses(cost, p)
+    for l in REGNET_LAYERS:
+        if l.name in y:                                    # 3dconv0_1 came out of the fused pass
+            continue
+        if fused and l.name in REGNET_PAIR:
+            s_pair = [stats(n) for n in REGNET_PAIR]
+            outs = conv3d_pair(cost, *(p[n]["w"] for n in REGNET_PAIR), *s_pair)
+            for n, out, s in zip(REGNET_PAIR, outs, s_pair):
+                batch_norm(n, out, s)
+            continue
+        s = stats(l.name) if l.bn else None
+        out = conv3d(y.get(l.p1, cost), p[l.name]["w"], l.stride, aff.get(l.p1), y.get(l.p2), aff.get(l.p2), s, l.kind == UP)
+        if l.bn:
+            batch_norm(l.name, out, s)
+    return out[..., 0], (cost, y, st, aff, sync)
 
 
 def regnet_backward(saved, p, g_reg):
@@ -256,73 +264,46 @@ def regnet_backward(saved, p, g_reg):
     the cost-volume backward."""
     cost, y, st, aff, sync = saved
     G: Dict[str, Dict[str, torch.Tensor]] = {}
-    g_reg = g_reg.contiguous()[..., None]
     nsl = _lib.load().mvs_bn_bwd_sum_slots()
-    slab = torch.zeros(nsl * sum(2 * y[n_].shape[-1] for n_ in st), device=g_reg.device, dtype=torch.float64)
-    used = [0]
+    take = _pieces(torch.zeros(nsl * sum(2 * y[n].shape[-1] for n in st), device=g_reg.device, dtype=torch.float64))
+    pending = {(None, REGNET_ORDER[-1]): g_reg.contiguous()[..., None]}      # (consumer, producer) -> gradient of a(producer)
+    acts, readers = {(): cost}, dict(_READERS)             # producers -> the activation their consumers read, while it has readers
 
-    def bn_bwd(name, g1, g2=None):
-        n_ = nsl * 2 * y[name].shape[-1]
-        sums = slab[used[0]:used[0] + n_]
-        used[0] += n_
-        g_y, gg, gb = bn_relu_bwd(y[name], st[name], aff[name], p[name]["gamma"], g1, g2, sync=sync, sums=sums)
-        G[name] = {"gamma": gg, "beta": gb}
-        return g_y
+    def input_act(l):
+        if l.srcs not in acts:
+            acts[l.srcs] = bn_relu(*(t for n in l.srcs for t in (y[n], aff[n])))
+        readers[l.srcs] -= 1
+        return acts[l.srcs] if readers[l.srcs] else acts.pop(l.srcs)
 
-    act = lambda n: bn_relu(y[n], aff[n])
-    # 3dconv6_2: conv 8 -> 1 on  s6 = a(6_0) + a(0_1), no BN
-    s6 = bn_relu(y["3dconv6_0"], aff["3dconv6_0"], y["3dconv0_1"], aff["3dconv0_1"])
-    G["3dconv6_2"] = {"w": conv3d_wgrad(s6, g_reg, 1)}
-    g_s6 = conv_s1_input_grad(g_reg, p["3dconv6_2"]["w"])
-    del s6
-    # 3dconv6_0: deconv 16 -> 8 on  s5 = a(5_0) + a(1_1)
-    g_y = bn_bwd("3dconv6_0", g_s6)
-    s5 = bn_relu(y["3dconv5_0"], aff["3dconv5_0"], y["3dconv1_1"], aff["3dconv1_1"])
-    G["3dconv6_0"]["w"] = conv3d_wgrad(g_y, s5, 2)
-    g_s5 = deconv_input_grad(g_y, p["3dconv6_0"]["w"])
-    # 3dconv0_1: conv 32 -> 8 on the cost volume
-    g_y = bn_bwd("3dconv0_1", g_s6)
-    # roles swapped (rows = the 8-channel gradient with its taps, columns = the 32 volume channels): the kernel packs 8
-    # taps per MFMA row tile; R(tap, c8, c32) = dW(2 - tap, c32, c8)
-    G["3dconv0_1"]["w"] = conv3d_wgrad(g_y, cost, 1).flip(0, 1, 2).permute(0, 1, 2, 4, 3).contiguous()
-    g_cost_a = conv_s1_input_grad(g_y, p["3dconv0_1"]["w"])
-    del g_s6
-    # 3dconv5_0: deconv 32 -> 16 on  s4 = a(4_0) + a(2_1)
-    g_y = bn_bwd("3dconv5_0", g_s5)
-    s4 = bn_relu(y["3dconv4_0"], aff["3dconv4_0"], y["3dconv2_1"], aff["3dconv2_1"])
-    G["3dconv5_0"]["w"] = conv3d_wgrad(g_y, s4, 2)
-    g_s4 = deconv_input_grad(g_y, p["3dconv5_0"]["w"])
-    # 3dconv1_1: conv 16 -> 16 on a(1_0)
-    a10 = act("3dconv1_0")
-    g_y = bn_bwd("3dconv1_1", g_s5)
-    G["3dconv1_1"]["w"] = conv3d_wgrad(a10, g_y, 1)
-    g_a10_b = conv_s1_input_grad(g_y, p["3dconv1_1"]["w"])
-    # 3dconv4_0: deconv 64 -> 32 on a(3_1)
-    g_y = bn_bwd("3dconv4_0", g_s4)
-    G["3dconv4_0"]["w"] = conv3d_wgrad(g_y, act("3dconv3_1"), 2)
-    g_a31 = deconv_input_grad(g_y, p["3dconv4_0"]["w"])
-    # 3dconv2_1: conv 32 -> 32 on a(2_0)
-    a20 = act("3dconv2_0")
-    g_y = bn_bwd("3dconv2_1", g_s4)
-    G["3dconv2_1"]["w"] = conv3d_wgrad(a20, g_y, 1)
-    g_a20_b = conv_s1_input_grad(g_y, p["3dconv2_1"]["w"])
-    # 3dconv3_1: conv 64 -> 64 on a(3_0)
-    g_y = bn_bwd("3dconv3_1", g_a31)
-    G["3dconv3_1"]["w"] = conv3d_wgrad(act("3dconv3_0"), g_y, 1)
-    g_a30 = conv_s1_input_grad(g_y, p["3dconv3_1"]["w"])
-    # 3dconv3_0: conv stride 2, 32 -> 64 on a(2_0)
-    g_y = bn_bwd("3dconv3_0", g_a30)
-    G["3dconv3_0"]["w"] = conv3d_wgrad(a20, g_y, 2)
-    g_a20_a = conv_s2_input_grad(g_y, p["3dconv3_0"]["w"])
-    # 3dconv2_0: conv stride 2, 16 -> 32 on a(1_0)
-    g_y = bn_bwd("3dconv2_0", g_a20_a, g_a20_b)
-    G["3dconv2_0"]["w"] = conv3d_wgrad(a10, g_y, 2)
-    g_a10_a = conv_s2_input_grad(g_y, p["3dconv2_0"]["w"])
-    # 3dconv1_0: conv stride 2, 32 -> 16 on the cost volume
-    g_y = bn_bwd("3dconv1_0", g_a10_a, g_a10_b)
-    G["3dconv1_0"]["w"] = conv3d_wgrad(cost, g_y, 2)
-    g_cost_b = conv_s2_input_grad(g_y, p["3dconv1_0"]["w"])
-    return G, g_cost_a, g_cost_b
+    def layer_backward(l):
+        name, w = l.name, p[l.name]["w"]
+        # a shared activation is recomputed ahead of its first reader's BatchNorm backward, any other behind it: the order of
+        # launches this pass has always had
+        x = input_act(l) if _READERS[l.srcs] > 1 or not l.bn else None
+        g_y = [pending.pop((c, name)) for c in REGNET_CONSUMERS[name] or (None,)]
+        if l.bn:
+            g_y, gg, gb = bn_relu_bwd(y[name], st[name], aff[name], p[name]["gamma"], *g_y, sync=sync,
+                                      sums=take(nsl * 2 * y[name].shape[-1]))
+            G[name] = {"gamma": gg, "beta": gb}
+        else:
+            g_y, = g_y
+            G[name] = {}
+        if x is None:
+            x = input_act(l)
+        dw = conv3d_wgrad(*((g_y, x) if l.wgrad_gradient_first else (x, g_y)), l.stride)
+        if l.wgrad_mirrored:
+            # roles swapped (rows = the 8-channel gradient with its taps, columns = the 32 volume channels): the kernel packs 8
+            # taps per MFMA row tile; R(tap, c8, c32) = dW(2 - tap, c32, c8)
+            dw = dw.flip(0, 1, 2).permute(0, 1, 2, 4, 3).contiguous()
+        G[name]["w"] = dw
+        del x
+        g_x = INPUT_GRAD[l.kind](g_y, w)
+        for src in l.srcs or (None,):
+            pending[(name, src)] = g_x
+
+    for name in REGNET_BACKWARD_ORDER:
+        layer_backward(REGNET_LAYER[name])
+    return (G,) + tuple(pending.pop((n, None)) for n in REGNET_PAIR)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -330,20 +311,13 @@ def regnet_backward(saved, p, g_reg):
 # ------------------------------------------------------------------------------------------------
 
 def flatten_params(p) -> List[torch.Tensor]:
-    out = []
-    for n in REGNET_ORDER:
-        out.append(p[n]["w"])
-        if n in BN_LAYERS:
-            out += [p[n]["gamma"], p[n]["beta"]]
-    return out
+    return [p[n][key] for n, key in REGNET_SLOTS]
 
 
 def unflatten_params(flat) -> Dict[str, Dict[str, torch.Tensor]]:
-    p, i = {}, 0
-    for n in REGNET_ORDER:
-        p[n] = {"w": flat[i]}; i += 1
-        if n in BN_LAYERS:
-            p[n]["gamma"], p[n]["beta"] = flat[i], flat[i + 1]; i += 2
+    p = {n: {} for n in REGNET_ORDER}
+    for (n, key), t in zip(REGNET_SLOTS, flat):
+        p[n][key] = t
     return p
 
 
@@ -375,11 +349,7 @@ class PlaneSweepDepth(torch.autograd.Function):
         G, ga, gb = regnet_backward(saved, p, g_reg)
         g_ref, g_src = cost_volume_bwd(features[0], features[1:], transforms, ga, gb)
         g_feat = torch.cat([g_ref[None], g_src], 0)
-        flat = []
-        for n in REGNET_ORDER:
-            flat.append(G[n]["w"])
-            if n in BN_LAYERS:
-                flat += [G[n]["gamma"], G[n]["beta"]]
+        flat = flatten_params(G)
         ctx.saved = None
         if ctx.into is not None:
             import ctypes as C

@@ -20,9 +20,8 @@ import torch
 from . import _lib
 from .feature_net import UNetDS2GN
 from .homography_warping import homography_transforms
+from .regnet_layers import BN_LAYERS, REGNET_LAYERS, REGNET_ORDER
 
-REGNET_ORDER = ("3dconv1_0", "3dconv2_0", "3dconv3_0", "3dconv0_1", "3dconv1_1", "3dconv2_1",
-                "3dconv3_1", "3dconv4_0", "3dconv5_0", "3dconv6_0", "3dconv6_2")
 GRU_CELL_KEYS = ("gates_w", "gates_b", "reset_gamma", "reset_beta", "update_gamma", "update_beta",
                  "out_w", "out_b", "out_gamma", "out_beta")
 BN_EPSILON = 1e-5      # mvsnet/cnn_wrapper/network.py:55
@@ -71,10 +70,11 @@ class RegNetWeights:
             if padded is not None:
                 params = padded
         self.w = [_dev(params[n]["w"], device) for n in REGNET_ORDER]
-        self.gamma = [_dev(params[n]["gamma"], device) for n in REGNET_ORDER[:-1]]
-        self.beta = [_dev(params[n]["beta"], device) for n in REGNET_ORDER[:-1]]
+        self.gamma = [_dev(params[n]["gamma"], device) for n in BN_LAYERS]
+        self.beta = [_dev(params[n]["beta"], device) for n in BN_LAYERS]
         self.cin = int(self.w[0].shape[3])
-        self.base = int(self.w[3].shape[4])           # 3dconv0_1: Cin -> base_filter
+        unit = next(i for i, l in enumerate(REGNET_LAYERS) if l.co == 1)      # a layer of base_filter output channels
+        self.base = int(REGNET_LAYERS[unit].cout_of(self.w[unit]))
         self.w_ptrs = _lib.ptr_array(self.w)
         self.g_ptrs = _lib.ptr_array(self.gamma)
         self.b_ptrs = _lib.ptr_array(self.beta)
@@ -217,40 +217,24 @@ def regnet_us0(cost_volume_, weights: RegNetWeights, workspace=None, out=None):
     """RegNetUS0 (mvsnetworks.py:122-158): (D,H,W,Cin) -> filtered cost volume (D,H,W); a 5-D (B,D,H,W,Cin) input is a
     batch whose BatchNorm layers share their statistics over (B,D,H,W) as in the reference (network.py:496-506)."""
     lib = _lib.load()
-    if cost_volume_.dim() == 5:
-        B, D, H, W, Cin = cost_volume_.shape
-        if Cin == weights.cin_native and Cin != weights.cin:
-            cost_volume_ = torch.nn.functional.pad(cost_volume_, (0, weights.cin - Cin)).contiguous()
-            Cin = weights.cin
-        if Cin != weights.cin:
-            raise _lib.MvsnetHipError("cost volume has %d channels, weights expect %d" % (Cin, weights.cin))
-        need = B * lib.mvs_regnet_workspace_bytes(D, H, W, Cin, weights.base)
-        if workspace is None:
-            workspace = torch.empty(need, device=cost_volume_.device, dtype=torch.uint8)
-        if out is None:
-            out = torch.empty((B, D, H, W), device=cost_volume_.device, dtype=torch.float32)
-        _lib.check(lib.mvs_regnet_us0_batch_f32(
-            _lib.ptr(_lib.f32(cost_volume_)), B, D, H, W, Cin, weights.base, weights.w_ptrs,
-            _lib.ptr(weights.prepared), weights.g_ptrs, weights.b_ptrs, BN_EPSILON,
-            C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(out), _lib.stream_ptr()),
-            "mvs_regnet_us0_batch_f32")
-        return out
-    D, H, W, Cin = cost_volume_.shape
+    *batch, D, H, W, Cin = cost_volume_.shape
+    if len(batch) > 1:
+        raise ValueError("cost volume must be (D,H,W,Cin) or (B,D,H,W,Cin), got %d dimensions" % cost_volume_.dim())
     if Cin == weights.cin_native and Cin != weights.cin:      # narrower mode running zero-padded (RegNetWeights)
         cost_volume_ = torch.nn.functional.pad(cost_volume_, (0, weights.cin - Cin)).contiguous()
         Cin = weights.cin
     if Cin != weights.cin:
         raise _lib.MvsnetHipError("cost volume has %d channels, weights expect %d" % (Cin, weights.cin))
-    need = lib.mvs_regnet_workspace_bytes(D, H, W, Cin, weights.base)
+    need = (batch[0] if batch else 1) * lib.mvs_regnet_workspace_bytes(D, H, W, Cin, weights.base)
     if workspace is None:
         workspace = torch.empty(need, device=cost_volume_.device, dtype=torch.uint8)
     if out is None:
-        out = torch.empty((D, H, W), device=cost_volume_.device, dtype=torch.float32)
-    _lib.check(lib.mvs_regnet_us0_prepared_f32(
-        _lib.ptr(_lib.f32(cost_volume_)), D, H, W, Cin, weights.base, weights.w_ptrs,
-        _lib.ptr(weights.prepared), weights.g_ptrs, weights.b_ptrs, BN_EPSILON,
-        C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(out), _lib.stream_ptr()),
-        "mvs_regnet_us0_prepared_f32")
+        out = torch.empty((*batch, D, H, W), device=cost_volume_.device, dtype=torch.float32)
+    entry, name = ((lib.mvs_regnet_us0_batch_f32, "mvs_regnet_us0_batch_f32") if batch else
+                   (lib.mvs_regnet_us0_prepared_f32, "mvs_regnet_us0_prepared_f32"))
+    _lib.check(entry(_lib.ptr(_lib.f32(cost_volume_)), *batch, D, H, W, Cin, weights.base, weights.w_ptrs,
+                     _lib.ptr(weights.prepared), weights.g_ptrs, weights.b_ptrs, BN_EPSILON,
+                     C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(out), _lib.stream_ptr()), name)
     return out
 
 

@@ -12,6 +12,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .regnet_layers import REGNET_LAYERS
+
 # Named workloads: (view_num N, depth planes D, feature H, feature W, depth_interval)
 # M  = BASELINE.json metric config; c1/c2/c3 = configs[0..2]; toy = golden-fixture size.
 WORKLOADS = {
@@ -101,26 +103,18 @@ def make_regnet_params(network_mode="normal", seed=1, in_channels=None, random_a
     b = base_filter(network_mode)
     cin0 = 4 * b if in_channels is None else in_channels
     rs = np.random.RandomState(seed)
-    spec = [
-        ("3dconv1_0", "conv", cin0, 2 * b), ("3dconv2_0", "conv", 2 * b, 4 * b),
-        ("3dconv3_0", "conv", 4 * b, 8 * b), ("3dconv0_1", "conv", cin0, b),
-        ("3dconv1_1", "conv", 2 * b, 2 * b), ("3dconv2_1", "conv", 4 * b, 4 * b),
-        ("3dconv3_1", "conv", 8 * b, 8 * b), ("3dconv4_0", "deconv", 8 * b, 4 * b),
-        ("3dconv5_0", "deconv", 4 * b, 2 * b), ("3dconv6_0", "deconv", 2 * b, b),
-        ("3dconv6_2", "conv", b, 1),
-    ]
     params = {}
-    for name, kind, cin, cout in spec:
-        shape = (3, 3, 3, cin, cout) if kind == "conv" else (3, 3, 3, cout, cin)
-        p = {"w": _he(rs, shape, 27 * cin)}
-        if name != "3dconv6_2":
+    for l in REGNET_LAYERS:
+        cin, cout = l.channels(cin0, b)
+        p = {"w": _he(rs, l.w_shape(cin, cout), 27 * cin)}
+        if l.bn:
             if random_affine:
                 p["gamma"] = (1.0 + 0.2 * rs.standard_normal(cout)).astype(np.float32)
                 p["beta"] = (0.1 * rs.standard_normal(cout)).astype(np.float32)
             else:
                 p["gamma"] = np.ones(cout, np.float32)
                 p["beta"] = np.zeros(cout, np.float32)
-        params[name] = p
+        params[l.name] = p
     return params
 
 
