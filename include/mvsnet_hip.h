@@ -71,7 +71,11 @@ int mvs_get_conv_impl(void);
 #define MVS_HOOK_OUT_PLANES           10  /* >= 1: planes per workgroup of 3dconv6_2 (tests reach several chunks and both march directions at small sizes; measurement); 0 (default) = the launcher's choice.  Chunks march in alternating directions: last bits */
 #define MVS_HOOK_BN_SLOTS             11  /* 1..8: partial rows of RegNetUS0's BatchNorm sums (every layer but the fused pair); 0 (default) = the built-in count.  The sums arrive in another order: last bits */
 #define MVS_HOOK_PAIR_SLOTS           12  /* 1..8: partial rows of the fused 3dconv0_1 + 1_0 pass's sums; 0 (default) = the built-in count.  Last bits, as above */
-#define MVS_HOOK_COUNT                13
+#define MVS_HOOK_CONV_FULL_SWEEPS     13  /* a + 4 * b, a for the 32 -> 8 kernels (conv3d_c8.hip), b for conv3d_s1_kernel (conv3d_mfma.hip), each 0..2.  1: every staged plane of a workgroup's range is swept in full, the halo planes d0 - 1 and d1 included; 2: but for halo planes outside the volume (A/B measurements, bit-equality tests); 0 (default): halo planes issue only the tiles whose result is kept, planes outside the volume none.  Same bits (an exact zero may change sign) */
+#define MVS_HOOK_PAIR_PLANES          14  /* even, >= 2: planes per workgroup of the fused 3dconv0_1 + 1_0 launch, in whole chunks (no SPAN); 0 (default) = the launcher's choice.  BatchNorm sums arrive in another order: last bits */
+#define MVS_HOOK_S1_PLANES            15  /* >= 1: planes per workgroup of the stride-1 plane-march kernels (conv3d_s1_kernel and the unfused 32 -> 8 kernel); 0 (default) = the launcher's choice.  Last bits, as above */
+#define MVS_HOOK_SPAN_FORCE           16  /* G << 8 | M (G = 1..8 tiles per group, M = G..16 ranges): the fused 3dconv0_1 + 1_0 launch takes the SPAN schedule with that pair at any size, if the launcher's other rules allow it (whole chunks if not); 0 (default) = the launcher's choice.  Last bits, as above */
+#define MVS_HOOK_COUNT                17
 int mvs_set_test_hook(int id, int value);
 int mvs_get_test_hook(int id);
 

@@ -71,6 +71,10 @@ struct FuseArgs {
     // boundary (two segments).  See launch_c8.
     int span_g, span_m;
     int span_b[17];
+    // test hook MVS_HOOK_CONV_FULL_SWEEPS.  1: every staged plane of a range is swept in full, the halo planes d0 - 1 and d1
+    // included -- what the kernel did before the halo planes were trimmed (see the plane march); 2: only halo planes outside
+    // the volume are left out.  Same bits.
+    int full_sweeps;
 };
 
 template <bool FUSE, bool AFF, bool SPAN = false>
@@ -186,9 +190,10 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
     const int a_lane = (kq * NROWS + (n & 7)) * 4;
 
     // `extra(G)` is called once per step: the plane march hangs the next plane's staging on it so
-    // that those VALU / LDS-write / global-load instructions issue in the shadow of the MFMAs
-    auto sweep = [&](auto Pc, const float* buf, auto&& extra) __attribute__((always_inline)) {
-        constexpr int P = decltype(Pc)::value;
+    // that those VALU / LDS-write / global-load instructions issue in the shadow of the MFMAs.
+    // TM (bit t = tile acc[t] is issued) is 7 on every plane but a range's first and last, whose other blocks retire() drops.
+    auto sweep = [&](auto Pc, auto Mc, const float* buf, auto&& extra) __attribute__((always_inline)) {
+        constexpr int P = decltype(Pc)::value, TM = decltype(Mc)::value;
         constexpr int KD_B0 = P % 3, KD_B1 = (P + 2) % 3, KD_B2 = (P + 1) % 3;
         const int a0 = a_lane + (hi ? KD_B1 : KD_B0) * COUT * 4;          // blocks 0|1
         const int ap = a_lane + KD_B2 * COUT * 4 - hi * KH_FLOATS;        // block 2: kh = i - hi
@@ -229,7 +234,7 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
                     else if (i == 0) { t = 0; aval = av[0][j]; }
                     else if (c == 0) { t = 1; aval = av[i - 1][j]; }
                     else { t = 0; aval = av[i][j]; }
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aval, bv[G & 1][j], acc[t], 0, 0, 0);
+                    if ((TM >> t) & 1) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aval, bv[G & 1][j], acc[t], 0, 0, 0);
                 }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -295,7 +300,9 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
     }
 
     auto s2_sweep = [&](auto Ec, const float* buf) __attribute__((always_inline)) {
-        constexpr bool EVEN = decltype(Ec)::value;   // even plane: kd 0 -> cur, kd 2 -> prv; odd: kd 1 -> cur
+        // 0: odd plane, kd 1 -> cur;  1: even plane, kd 0 -> cur, kd 2 -> prv;  2: the even plane that ends a range, kd 2 -> prv
+        // only (the output plane it would start belongs to the next range)
+        constexpr int MODE = decltype(Ec)::value;
         f32x2 b2[2][2];
         auto ld = [&](int tap, f32x2 (&b)[2]) __attribute__((always_inline)) {
             const int kh = tap / 3, kw = tap % 3;
@@ -311,8 +318,8 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
                     const float bval = b2[tap & 1][ct][j];
-                    if (EVEN) {
-                        cur[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS[0][tap][j], bval, cur[ct], 0, 0, 0);
+                    if (MODE) {
+                        if (MODE == 1) cur[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS[0][tap][j], bval, cur[ct], 0, 0, 0);
                         prv[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS[2][tap][j], bval, prv[ct], 0, 0, 0);
                     } else {
                         cur[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS[1][tap][j], bval, cur[ct], 0, 0, 0);
@@ -349,13 +356,23 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
     // from global memory (steps 14..19).  The two workgroups of a CU fall into lock-step (the one that
     // is behind gets the whole matrix pipe while the other waits at its barrier), so whatever is NOT
     // hidden under the MFMAs is idle time for both: only the retire stores and the barrier are left.
-    auto prologue = [&]() __attribute__((always_inline)) {
+    //
+    // Halo planes.  A range [d0, d1) stages the input planes d0 - 1 .. d1 (t = 0 .. T - 1, P = t % 3), but its first and last
+    // plane feed one output plane each, and retire() drops the rest of what a full sweep of them would add:
+    //   * plane d0 - 1 is kd = 0 of output d0 alone, block 0 = the tiles acc[0] | acc[1]; the packed tile (96 of the 240
+    //     MFMAs) is left out (first_plane).  With d0 = 0 the plane is SAME padding: the march starts at t = 1 instead;
+    //   * plane d1 is kd = 2 of output d1 - 1 alone, block (P + 1) % 3: the packed tile when that is block 2, acc[0] | acc[1]
+    //     otherwise, and of the stride-2 part the kd = 2 half (last_plane; d1 is even in the fused kernel).  With d1 = D the
+    //     plane is padding and nothing is swept.  Nothing is staged behind a range's last plane either.
+    // The planes between them run plane() as before.  fa.full_sweeps = 1 runs plane() on all T planes, 2 on all inside the volume.
+    auto prologue = [&](int t0) __attribute__((always_inline)) {
+        float* buf = slab + (t0 & 1) * SLAB_FLOATS;
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) load_piece(i, d0 - 1);
+        for (int i = 0; i < NIT; ++i) load_piece(i, d0 - 1 + t0);
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) stage_piece(i, d0 - 1, slab);
+        for (int i = 0; i < NIT; ++i) stage_piece(i, d0 - 1 + t0, buf);
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) load_piece(i, d0);
+        for (int i = 0; i < NIT; ++i) load_piece(i, d0 + t0);
         __syncthreads();
     };
 
@@ -370,7 +387,7 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
             if (G >= 14 && G < 14 + NIT) load_piece(G - 14, q + 2);
         };
         if (FUSE) s2_finish();
-        sweep(Pc, cur_buf, extra);                 // planes outside the volume are staged as zeros
+        sweep(Pc, std::integral_constant<int, 7>{}, cur_buf, extra);      // planes outside the volume are staged as zeros
         if (FUSE && q >= d0) {
             if (q & 1) {
                 if (in_vol) s2_sweep(std::false_type{}, cur_buf);
@@ -393,6 +410,44 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
         retire(Pc, q - 1);
         __syncthreads();
     };
+    // t = 0 of a range that starts inside the volume (P = 0)
+    auto first_plane = [&]() __attribute__((always_inline)) {
+        const int q = d0 - 1;
+        float* nxt = slab + SLAB_FLOATS;
+        auto extra = [&](int G) __attribute__((always_inline)) {
+            if (G >= 6 && G < 6 + NIT) stage_piece(G - 6, q + 1, nxt);
+            if (G >= 14 && G < 14 + NIT) load_piece(G - 14, q + 2);
+        };
+        sweep(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, slab, extra);
+        retire(std::integral_constant<int, 0>{}, q - 1);      // (zeroes what block 1 took)
+        __syncthreads();
+    };
+    // t = T - 1, plane d1
+    auto last_plane = [&](auto Pc) __attribute__((always_inline)) {
+        constexpr int P = decltype(Pc)::value;
+        const int q = d1;
+        const float* cur_buf = slab + ((T - 1) & 1) * SLAB_FLOATS;
+        const bool in_vol = q < a.D;
+        if (FUSE) s2_finish();
+        if (in_vol) sweep(Pc, std::integral_constant<int, (P + 1) % 3 == 2 ? 4 : 3>{}, cur_buf, [](int) {});
+        if (FUSE) {
+            // plane q = 2*od_cur completes od_cur - 1 (kd 2); od_cur is another range's
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) { prv[ct] = cur[ct]; cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+            if (in_vol) s2_sweep(std::integral_constant<int, 2>{}, cur_buf);
+            const int od_prev = q / 2 - 1;
+            if (2 * od_prev >= d0) {
+                if (wave > 0) {
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct)
+                        *(f32x4*)(red + (((wave - 1) * 2 + ct) * 64 + lane) * 4) = prv[ct];
+                }
+                fin_od = od_prev;
+            }
+        }
+        retire(Pc, q - 1);
+        __syncthreads();
+    };
     for (int sg = 0; sg < (SPAN ? nseg : 1); ++sg) {
         if (SPAN && sg > 0) {
             // second segment: another tile, its first planes.  Whatever the first march left in the accumulators belongs to
@@ -408,11 +463,22 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
                 for (int ct = 0; ct < 2; ++ct) { cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; prv[ct] = cur[ct]; }
             }
         }
-        prologue();
-        for (int t = 0; t < T; t += 3) {
-            plane(std::integral_constant<int, 0>{}, t);
-            if (t + 1 < T) plane(std::integral_constant<int, 1>{}, t + 1);
-            if (t + 2 < T) plane(std::integral_constant<int, 2>{}, t + 2);
+        // planes [t_lo, t_hi) run plane(); T >= 3, so the first and the last plane are two planes
+        const bool trim_first = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d0 == 0);
+        const bool trim_last = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d1 == a.D);
+        const int t_lo = trim_first ? 1 : 0, t_hi = trim_last ? T - 1 : T;
+        prologue(trim_first && d0 == 0 ? 1 : 0);
+        if (trim_first && d0 > 0) first_plane();
+        for (int t = 0; t < t_hi; t += 3) {
+            if (t >= t_lo) plane(std::integral_constant<int, 0>{}, t);
+            if (t + 1 < t_hi) plane(std::integral_constant<int, 1>{}, t + 1);
+            if (t + 2 < t_hi) plane(std::integral_constant<int, 2>{}, t + 2);
+        }
+        if (trim_last) {
+            const int pl = (T - 1) % 3;
+            if (pl == 0) last_plane(std::integral_constant<int, 0>{});
+            else if (pl == 1) last_plane(std::integral_constant<int, 1>{});
+            else last_plane(std::integral_constant<int, 2>{});
         }
     }
     if (FUSE) {
@@ -439,8 +505,12 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
 }
 
 template <bool FUSE>
-int launch_c8(const ConvArgs& a0, const FuseArgs& fa, hipStream_t st) {
+int launch_c8(const ConvArgs& a0, const FuseArgs& fa0, hipStream_t st) {
     ConvArgs a = a0;
+    FuseArgs fa = fa0;
+    fa.full_sweeps = mvs_hook(MVS_HOOK_CONV_FULL_SWEEPS) & 3;
+    // test hooks: planes per workgroup (whole chunks then, no SPAN), or SPAN with a given (G, M)
+    const int hk_planes = mvs_hook(FUSE ? MVS_HOOK_PAIR_PLANES : MVS_HOOK_S1_PLANES), hk_span = mvs_hook(MVS_HOOK_SPAN_FORCE);
     if ((long long)a.D * a.H * a.W * CIN * 4 >= (1LL << 31)) return MVS_E_SHAPE;   // 32-bit buffer offsets
     const int tiles = ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
     if (FUSE) {
@@ -455,6 +525,7 @@ int launch_c8(const ConvArgs& a0, const FuseArgs& fa, hipStream_t st) {
     } else {
         a.planes_per_wg = conv_pick_planes(a.D, tiles, 2);
     }
+    if (hk_planes) a.planes_per_wg = hk_planes < a.D ? hk_planes : a.D;
     dim3 grid(tiles, 1, (a.D + a.planes_per_wg - 1) / a.planes_per_wg);
     const size_t smem = (size_t)(LDS_FLOATS + (FUSE ? RED_FLOATS : 0)) * sizeof(float);
     const bool aff = a.xs != nullptr || a.bn.stats != nullptr;
@@ -479,18 +550,22 @@ int launch_c8(const ConvArgs& a0, const FuseArgs& fa, hipStream_t st) {
         // steps), 5 tiles / 16 workgroups fill every slot with ranges of 60 (60 + 3, + 2 across a boundary): 581 -> 565 us,
         // 921 -> 935 depth maps/s on one box.  Ranges 8 planes shorter across a boundary (62 / 54) and a pairing of long with
         // short ranges on a CU measured the same (profiles/r04_pair_span_ab.txt).
-        if (!aff && !mvs_hook(MVS_HOOK_CONV_NO_SPAN)) {      // (test hook: whole depth chunks, the schedule SPAN replaces)
+        if (!aff && !mvs_hook(MVS_HOOK_CONV_NO_SPAN) && !hk_planes) {      // (test hook: whole depth chunks, the schedule SPAN replaces)
             const long long chunk_cost = (((long long)tiles * grid.z + 511) / 512) * (a.planes_per_wg + 3);
             int bg = 0, bm = 0; long long bcost = chunk_cost;
+            // MVS_HOOK_SPAN_FORCE = G << 8 | M: that pair alone is looked at, at any range length and whatever it costs (tests
+            // reach ranges that cross a tile boundary at small sizes); a pair that breaks the other rules falls back to chunks
+            const int fg = hk_span >> 8, fm = hk_span & 255;
             for (int G = 1; G <= 8; ++G) {
-                if (tiles % G) continue;
+                if (tiles % G || (hk_span && G != fg)) continue;
                 for (int M = G; M <= 16; ++M) {
+                    if (hk_span && M != fm) continue;
                     const int total = G * a.D;
                     if (total % M || (long long)(tiles / G) * M > 512) continue;
                     const int L = total / M;
-                    if ((L & 1) || L < 32 || L > a.D) continue;          // even starts (stride-2 planes), at most one boundary per range
+                    if ((L & 1) || (L < 32 && !hk_span) || L > a.D) continue;      // even starts (stride-2 planes), at most one boundary per range
                     const long long cost = L + 3 + ((a.D % L) ? 2 : 0);
-                    if (cost < bcost) { bcost = cost; bg = G; bm = M; }
+                    if (cost < bcost || hk_span) { bcost = cost; bg = G; bm = M; }
                 }
             }
             if (bg) {

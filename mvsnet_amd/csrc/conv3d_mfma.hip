@@ -65,6 +65,7 @@ struct Fuse2Args {
     float* y2;            // (D/2, H/2, W/2, 32) raw output
     double* stats2;       // (slots2, 2, 32) float64 sums or null
     int slots2;
+    int full_sweeps;      // test hook MVS_HOOK_CONV_FULL_SWEEPS: 1 = halo planes are swept in full, 2 = but for those outside the volume; see the plane march
 };
 constexpr int FUSE2_RED_FLOATS = 3 * 2 * 2 * 64 * 4;      // partial tiles of waves 1..3: [wave][row tile][column tile][lane][4]
 
@@ -210,9 +211,10 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
     // One plane sweep; P = plane counter mod 3 (static), block b carries kd = (P - b) mod 3.
     // `extra(g)` is called once per operand group: the plane march hangs the next planes' staging on
     // it, so that those VALU / LDS-write / global-load instructions issue between the MFMAs.
+    // TM (bit m = row tile m is issued) is all ones on every plane but a range's first and last.
     constexpr int NG = 9 * (CIN / 16);
-    auto sweep = [&](auto Pc, const float* buf, auto&& extra) __attribute__((always_inline)) {
-        constexpr int P = decltype(Pc)::value;
+    auto sweep = [&](auto Pc, auto Mc, const float* buf, auto&& extra) __attribute__((always_inline)) {
+        constexpr int P = decltype(Pc)::value, TM = decltype(Mc)::value;
         int a_off[MT];
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
@@ -244,7 +246,7 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
                     for (int v = 0; v < V; ++v)
-                        acc[m][v] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[g & 1][m][j], bv[g & 1][v][j], acc[m][v], 0, 0, 0);
+                        if ((TM >> m) & 1) acc[m][v] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[g & 1][m][j], bv[g & 1][v][j], acc[m][v], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -315,7 +317,8 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
     // plane's four MFMAs per tap do not cover an LDS read's latency).  (Hanging the taps between the operand groups of the
     // stride-1 sweep instead was measured slower, round 4: 109-112 us for the fused launch against 100 us.)
     auto s2_sweep = [&](auto Ec, const float* buf) __attribute__((always_inline)) {
-        constexpr bool EVEN = decltype(Ec)::value;   // even plane: kd 0 -> cur, kd 2 -> prv; odd: kd 1 -> cur
+        // 0: odd plane, kd 1 -> cur;  1: even plane, kd 0 -> cur, kd 2 -> prv;  2: the even plane that ends a range, kd 2 -> prv only
+        constexpr int MODE = decltype(Ec)::value;
         float b2[3][2];
         auto ld = [&](int tap, float (&b)[2]) __attribute__((always_inline)) {
             const int kh = tap / 3, kw = tap % 3;
@@ -331,8 +334,8 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
                     const float bval = b2[tap % 3][ct];
-                    if (EVEN) {
-                        cur2[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS2[0][tap][rt], bval, cur2[rt][ct], 0, 0, 0);
+                    if (MODE) {
+                        if (MODE == 1) cur2[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS2[0][tap][rt], bval, cur2[rt][ct], 0, 0, 0);
                         prv2[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS2[FUSE2 ? 2 : 0][tap][rt], bval, prv2[rt][ct], 0, 0, 0);
                     } else {
                         cur2[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS2[FUSE2 ? 1 : 0][tap][rt], bval, cur2[rt][ct], 0, 0, 0);
@@ -372,13 +375,27 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
     // Plane q is swept while plane q+1 moves registers -> LDS (first half of the operand groups) and
     // plane q+2 is requested from global memory (second half): with one or two waves per SIMD,
     // whatever is not issued under the MFMAs is idle matrix-pipe time.
+    //
+    // Halo planes.  A range [d0, d1) stages the input planes d0 - 1 .. d1 (t = 0 .. T - 1, P = t % 3), but its first and last
+    // plane feed one output plane each and retire() drops the rest of what a full sweep of them would add: plane d0 - 1 is
+    // kd = 0 of output d0 alone (block 0, row tile 0: first_plane), plane d1 is kd = 2 of output d1 - 1 alone (block
+    // (P + 1) % 3, one row tile, and of the fused stride-2 part the kd = 2 half: last_plane; d1 is even there).  With
+    // COUT = 16 a block is a row tile; with COUT = 8 blocks 0 | 1 share tile 0, so whole tiles are all that can be left out.
+    // With d0 = 0 plane -1 is SAME padding and the march starts at t = 1; with d1 = D plane D is padding and nothing is swept.
+    // Nothing is staged behind a range's last plane.  fa.full_sweeps = 1 runs plane() on all T planes, 2 on all inside the volume.
+    const bool trim_first = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d0 == 0);
+    const bool trim_last = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d1 == a.D);
+    const int t_first = trim_first && d0 == 0 ? 1 : 0;
+    {
+        float* buf = slab + (t_first & 1) * SLAB_FLOATS;
 #pragma unroll
-    for (int i = 0; i < NIT; ++i) load_piece(i, d0 - 1);
+        for (int i = 0; i < NIT; ++i) load_piece(i, d0 - 1 + t_first);
 #pragma unroll
-    for (int i = 0; i < NIT; ++i) stage_piece(i, d0 - 1, slab);
+        for (int i = 0; i < NIT; ++i) stage_piece(i, d0 - 1 + t_first, buf);
 #pragma unroll
-    for (int i = 0; i < NIT; ++i) load_piece(i, d0);
-    __syncthreads();
+        for (int i = 0; i < NIT; ++i) load_piece(i, d0 + t_first);
+        __syncthreads();
+    }
 
     auto plane = [&](auto Pc, int t) __attribute__((always_inline)) {
         const int q = d0 - 1 + t;
@@ -393,7 +410,7 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
             }
         };
         if (FUSE2) s2_finish();
-        sweep(Pc, cur, extra);                      // planes outside the volume are staged as zeros
+        sweep(Pc, std::integral_constant<int, (1 << MT) - 1>{}, cur, extra);      // planes outside the volume are staged as zeros
         if (FUSE2 && q >= d0) {
             const bool in_vol = q < a.D;
             if (q & 1) {
@@ -421,10 +438,65 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
         retire(Pc, q - 1);
         __syncthreads();
     };
-    for (int t = 0; t < T; t += 3) {
-        plane(std::integral_constant<int, 0>{}, t);
-        if (t + 1 < T) plane(std::integral_constant<int, 1>{}, t + 1);
-        if (t + 2 < T) plane(std::integral_constant<int, 2>{}, t + 2);
+    // t = 0 of a range that starts inside the volume (P = 0)
+    auto first_plane = [&]() __attribute__((always_inline)) {
+        const int q = d0 - 1;
+        float* nxt = slab + SLAB_FLOATS;
+        auto extra = [&](int g) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < NIT; ++i) {
+                if ((i * (NG / 2)) / NIT == g) stage_piece(i, q + 1, nxt);
+                if (NG / 2 + (i * (NG - NG / 2)) / NIT == g) load_piece(i, q + 2);
+            }
+        };
+        sweep(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, slab, extra);
+        retire(std::integral_constant<int, 0>{}, q - 1);      // (zeroes what block 1 took, if it shares tile 0)
+        __syncthreads();
+    };
+    // t = T - 1, plane d1
+    auto last_plane = [&](auto Pc) __attribute__((always_inline)) {
+        constexpr int P = decltype(Pc)::value;
+        constexpr int mt = (((P + 1) % 3) * COUT) / 16;      // row tile of the block that completes
+        const int q = d1;
+        const float* cur = slab + ((T - 1) & 1) * SLAB_FLOATS;
+        const bool in_vol = q < a.D;
+        if (FUSE2) s2_finish();
+        if (in_vol) sweep(Pc, std::integral_constant<int, 1 << mt>{}, cur, [](int) {});
+        if (FUSE2) {
+            // plane q = 2 * od_cur completes od_cur - 1 (kd 2); od_cur is another range's
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) { prv2[rt][ct] = cur2[rt][ct]; cur2[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+            if (in_vol) s2_sweep(std::integral_constant<int, 2>{}, cur);
+            const int od_prev = q / 2 - 1;
+            if (2 * od_prev >= d0) {
+                if (wave > 0) {
+#pragma unroll
+                    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                        for (int ct = 0; ct < 2; ++ct)
+                            *(f32x4*)(red2 + ((((wave - 1) * 2 + rt) * 2 + ct) * 64 + lane) * 4) = prv2[rt][ct];
+                }
+                fin_od = od_prev;
+            }
+        }
+        retire(Pc, q - 1);
+        __syncthreads();
+    };
+    // planes [t_lo, t_hi) run plane(); T >= 3, so the first and the last plane are two planes
+    const int t_lo = trim_first ? 1 : 0, t_hi = trim_last ? T - 1 : T;
+    if (trim_first && d0 > 0) first_plane();
+    for (int t = 0; t < t_hi; t += 3) {
+        if (t >= t_lo) plane(std::integral_constant<int, 0>{}, t);
+        if (t + 1 < t_hi) plane(std::integral_constant<int, 1>{}, t + 1);
+        if (t + 2 < t_hi) plane(std::integral_constant<int, 2>{}, t + 2);
+    }
+    if (trim_last) {
+        const int pl = (T - 1) % 3;
+        if (pl == 0) last_plane(std::integral_constant<int, 0>{});
+        else if (pl == 1) last_plane(std::integral_constant<int, 1>{});
+        else last_plane(std::integral_constant<int, 2>{});
     }
 
     if (FUSE2) {
@@ -460,6 +532,8 @@ int launch_s1(const ConvArgs& a0, int Cout, hipStream_t st, int slots = 256) {
     const int tiles = ((a.H + TH - 1) / TH) * ((a.W + TWG - 1) / TWG);
     const int groups = Cout / COUT;
     a.planes_per_wg = conv_pick_planes(a.D, (long long)tiles * groups, 2, slots);
+    if (const int hk = mvs_hook(MVS_HOOK_S1_PLANES)) a.planes_per_wg = hk < a.D ? hk : a.D;      // tests
+    const Fuse2Args fa = {nullptr, nullptr, nullptr, 0, (mvs_hook(MVS_HOOK_CONV_FULL_SWEEPS) >> 2) & 3};
     dim3 grid(tiles, groups, (a.D + a.planes_per_wg - 1) / a.planes_per_wg);
     size_t smem = (size_t)S1Geom<CIN, COUT, TH, TWG>::LDS_BYTES;
     static bool attr_done = false;       // per template instantiation
@@ -471,8 +545,8 @@ int launch_s1(const ConvArgs& a0, int Cout, hipStream_t st, int slots = 256) {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)) != hipSuccess) return (int)e;
         attr_done = true;
     }
-    if (a.x2) conv3d_s1_kernel<CIN, COUT, TH, true, TWG, CR><<<grid, 256, smem, st>>>(a, Fuse2Args{});
-    else conv3d_s1_kernel<CIN, COUT, TH, false, TWG, CR><<<grid, 256, smem, st>>>(a, Fuse2Args{});
+    if (a.x2) conv3d_s1_kernel<CIN, COUT, TH, true, TWG, CR><<<grid, 256, smem, st>>>(a, fa);
+    else conv3d_s1_kernel<CIN, COUT, TH, false, TWG, CR><<<grid, 256, smem, st>>>(a, fa);
     return (int)hipGetLastError();
 }
 
@@ -541,7 +615,7 @@ int mvs_conv3d_dispatch(ConvArgs& a, int Cin, int Cout, int stride, hipStream_t 
 // 3dconv1_1 (x -> y, 16 -> 16, stride 1) and 3dconv2_0 (x -> y2, 16 -> 32, stride 2) over the same BN + ReLU input in one pass
 int mvs_conv3d_s1_fuse2_launch(const ConvArgs& a, const float* w2, float* y2, double* stats2, hipStream_t st) {
     if (mvs_hook(MVS_HOOK_CONV_NO_FUSE2)) return MVS_E_SHAPE;      // test hook: the caller then runs the two layers apart (tests/test_gpu_parity.py)
-    return launch_s1_fuse2(a, Fuse2Args{w2, y2, stats2, a.stats_slots}, st);
+    return launch_s1_fuse2(a, Fuse2Args{w2, y2, stats2, a.stats_slots, (mvs_hook(MVS_HOOK_CONV_FULL_SWEEPS) >> 2) & 3}, st);
 }
 
 // ---- weight pre-layout (run once per weight set, mvs_regnet_prepare_f32) ---------------------------
