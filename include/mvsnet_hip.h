@@ -422,7 +422,8 @@ int mvs_gru_fused_trace(void* buffer, int capacity);
 int mvs_gru_stream_layout(void* stream, int* pipe_of_caller, float* probe_us);
 
 /* ---------------------------------------------------------------------------------------------
- * backward passes of the plane-sweep path for training.  The reference has no such
+ * backward passes of the plane-sweep path for training (csrc/backward.hip, conv3d_wgrad.hip; the
+ * optimiser steps: csrc/optimizer.hip).  The reference has no such
  * functions: TensorFlow differentiates the graph of `inference` (mvsnet/model.py:257-372) inside
  * opt.compute_gradients (mvsnet/train.py:428-429).  Input gradients of the 3D convolutions need no
  * entry point of their own: a stride-2 convolution's input gradient is mvs_deconv3d_f32 with the SAME
@@ -486,7 +487,7 @@ int mvs_cost_volume_bwd_gather_f32(const float* ref, const float* src, const flo
                                    float* g_ref, float* g_src, void* stream);
 int mvs_rmsprop_step_f32(float* w, const float* g, float* ms, float* mom, size_t n, float lr,
                          float decay, float momentum, float eps, float grad_scale, void* stream);
-/* GroupNorm (+ReLU) of the 2D towers for TRAINING (Network.conv_gn / deconv_gn, network.py:217-276, 350-409:
+/* GroupNorm (+ReLU) of the 2D towers for TRAINING (csrc/groupnorm.hip; Network.conv_gn / deconv_gn, network.py:217-276, 350-409:
  * groups of 8 channels, biased variance; inference fuses GroupNorm into mvs_conv2d_gn_f32 instead).
  *   x, y, g, dx   (V, hw, C) channel-last, C a multiple of 8
  *   stats         (V, 2, C) float64 per-channel [sum, sum of squares] of x, zeroed by the caller before
@@ -519,7 +520,7 @@ int mvs_gn_bwd_apply_f32(const float* x, const double* stats, const float* gamma
 int mvs_gn_bwd_apply_tot_f32(const float* x, const double* stats, const float* gamma, const float* beta, float eps,
                              int relu, const float* g, const double* sums, double* totals, int V, size_t hw, int C, float* dx,
                              void* stream);
-/* The other two optimisers of setup_optimizer (train.py:248-271): tf.train.MomentumOptimizer
+/* The other two optimisers of setup_optimizer (csrc/optimizer.hip; train.py:248-271): tf.train.MomentumOptimizer
  * (accum = momentum*accum + g; w -= lr*accum) and tf.train.AdamOptimizer (lr_t = lr*sqrt(1-beta2^t)/
  * (1-beta1^t) formed by the caller; w -= lr_t*m/(sqrt(v)+eps)). */
 int mvs_momentum_step_f32(float* w, const float* g, float* accum, size_t n, float lr, float momentum,

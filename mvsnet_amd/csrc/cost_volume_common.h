@@ -24,13 +24,21 @@ __device__ __forceinline__ float4 fma4(float w, float4 a, float4 acc) {
     return acc;
 }
 
+// The projective image (sx, sy) of pixel (x, y) under the plane transform t[0..8): the one statement of it for the forward's
+// taps, the backward's taps and the gather backward's candidate match.  (The compiler still chooses per kernel which products
+// it fuses into the sums, so two kernels may differ in the last bit; each kernel is consistent with itself.)
+__device__ __forceinline__ void warp_point(const float* __restrict__ t, float xf, float yf, float& sx, float& sy) {
+    float proj = t[6] * xf + t[7] * yf + 1.0f;
+    sx = (t[0] * xf + t[1] * yf + t[2]) / proj;
+    sy = (t[3] * xf + t[4] * yf + t[5]) / proj;
+}
+
 // Bilinear sample of `img` (H,W,C) at the projective image of pixel (x,y); channels [c, c+4).
 template <int BORDER>
 __device__ __forceinline__ float4 warp_sample(const float* __restrict__ img, const float* __restrict__ t,
                                               float xf, float yf, int H, int W, int C, int c) {
-    float proj = t[6] * xf + t[7] * yf + 1.0f;
-    float sx = (t[0] * xf + t[1] * yf + t[2]) / proj;
-    float sy = (t[3] * xf + t[4] * yf + t[5]) / proj;
+    float sx, sy;
+    warp_point(t, xf, yf, sx, sy);
     float x0 = floorf(sx), y0 = floorf(sy);
     float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
     float4 z = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -7,18 +7,9 @@
 // Roofline: HBM, D*H*W*4 bytes in (+8 bytes/pixel out).  Block = 64 consecutive pixels x 4 depth
 // groups (wave g sweeps planes g, g+4, ...), combined through LDS.
 #include "common.h"
+#include "softargmin_common.h"
 
 namespace {
-
-__device__ __forceinline__ float depth_at(int d, int D, float start, float interval, int inverse) {
-    float end = start + ((float)D - 1.0f) * interval;                    // model.py:378-379
-    float denom = (float)(D > 1 ? D - 1 : 1);
-    if (inverse) {                                                        // :481-485
-        float a = 1.0f / start, b = 1.0f / end;
-        return 1.0f / (a + (float)d * ((b - a) / denom));
-    }
-    return start + (float)d * ((end - start) / denom);                    // :487-488
-}
 
 // Tile variant: the block's 32 pixel columns (32 x D floats) are pulled into LDS with every load
 // in flight at once (the plain kernel below walks depth with a few dependent loads per thread and
@@ -72,23 +63,8 @@ softargmin_prob_tile_kernel(const float* __restrict__ reg, int D, int HW, float 
     const float dep = sz / se;                                            // model.py:493-494
     depth_out[pix] = dep;
 
-    int l0, r0;                                                           // model.py:83-140
-    if (inverse) {
-        float end = start + ((float)D - 1.0f) * interval;
-        float inv_s = 1.0f / start, inv_e = 1.0f / end;
-        float inv_int = (inv_s - inv_e) / ((float)D - 1.0f);
-        float idx = (1.0f / dep - inv_e) / inv_int;
-        l0 = D - (int)ceilf(idx) - 1;
-        r0 = D - (int)floorf(idx) - 1;
-    } else {
-        float idx = (dep - start) / interval;
-        l0 = (int)floorf(idx);
-        r0 = (int)ceilf(idx);
-    }
-    l0 = min(max(l0, 0), D - 1);
-    r0 = min(max(r0, 0), D - 1);
-    int l1 = min(max(l0 - 1, 0), D - 1);
-    int r1 = min(max(r0 + 1, 0), D - 1);
+    int l0, r0, l1, r1;                                                   // model.py:83-140
+    prob_buckets(dep, D, start, interval, inverse, l0, r0, l1, r1);
     float pl0 = tile[l0 * SA_PX + px] / se, pr0 = tile[r0 * SA_PX + px] / se;
     float pl1 = tile[l1 * SA_PX + px] / se, pr1 = tile[r1 * SA_PX + px] / se;
     prob_out[pix] = (pl0 + pr0) + (pl1 + pr1);
@@ -128,23 +104,8 @@ softargmin_prob_kernel(const float* __restrict__ reg, int D, int HW, float start
     depth_out[pix] = dep;
 
     // probability map: P[l0] + P[r0] + P[l1] + P[r1]   (model.py:83-140)
-    int l0, r0;
-    if (inverse) {
-        float end = start + ((float)D - 1.0f) * interval;
-        float inv_s = 1.0f / start, inv_e = 1.0f / end;
-        float inv_int = (inv_s - inv_e) / ((float)D - 1.0f);
-        float idx = (1.0f / dep - inv_e) / inv_int;
-        l0 = D - (int)ceilf(idx) - 1;
-        r0 = D - (int)floorf(idx) - 1;
-    } else {
-        float idx = (dep - start) / interval;
-        l0 = (int)floorf(idx);
-        r0 = (int)ceilf(idx);
-    }
-    l0 = min(max(l0, 0), D - 1);
-    r0 = min(max(r0, 0), D - 1);
-    int l1 = min(max(l0 - 1, 0), D - 1);
-    int r1 = min(max(r0 + 1, 0), D - 1);
+    int l0, r0, l1, r1;
+    prob_buckets(dep, D, start, interval, inverse, l0, r0, l1, r1);
     float pl0 = expf(-col[(size_t)l0 * HW] - m) / se;
     float pr0 = expf(-col[(size_t)r0 * HW] - m) / se;
     float pl1 = expf(-col[(size_t)l1 * HW] - m) / se;
