@@ -647,6 +647,34 @@ int mvs_nn_f32(const float* query, int n_query, const float* target, int n_targe
 int mvs_nn_query_f32(int n_query, int n_target, float ox, float oy, float oz, float cell, int gx, int gy, int gz,
                      float max_dist, float* dist, int* index, int* visited, const void* workspace, size_t workspace_bytes,
                      void* stream);
+/* The target's grid alone, built once for many queries against a target that does not move (count / scan / scatter of
+ * mvs_nn_f32 for the target only):
+ *   workspace     mvs_nn_target_workspace_bytes(n_target, gx, gy, gz) bytes (0 for invalid sizes); after the call it holds the
+ *                 per-cell starts, the cell-ordered float4 copy (x, y, z, input index) and each point's place in that copy */
+size_t mvs_nn_target_workspace_bytes(int n_target, int gx, int gy, int gz);
+int mvs_nn_target_build_f32(const float* target, int n_target, float ox, float oy, float oz, float cell, int gx, int gy, int gz,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* One step of point-to-point ICP, fused: transform, nearest neighbour and the float64 moments the host solves from
+ * (mvsnet_amd/register.py is normative):
+ *   source        (n_source,3) float32, read only
+ *   order         NULL or (n_source) int32, a permutation of the source: the order in which lanes take the points (points that
+ *                 share a target cell side by side run faster); NULL = input order.  It never changes which neighbour a
+ *                 point gets, only the order of the float64 sums
+ *   T, cp, cq     [host] row-major 3x4 float64 transform (finite) and the two float64 centres, passed to the kernel by value
+ *   grid, n_target, target_workspace: exactly what mvs_nn_target_build_f32 was called with and what it left behind
+ *   moments       [device] 18 doubles over the source points p whose p' = fl32(T p) (rows left to right in float64, rounded
+ *                 once) has a target point q with float32 d^2 <= max_corr_dist^2 (nearest, ties to the smallest index):
+ *                 count, sum |r|^2, sum a (3), sum b (3), sum a b^T (9, row-major), sum |a|^2 with a = p - cp, b = q - cq,
+ *                 r = T p - q in float64 (T p unrounded)
+ *   dist, index   NULL or (n_source) float32 / int32 in input order, as mvs_nn_f32 writes them for the queries p'
+ *   workspace     mvs_icp_step_workspace_bytes(n_source) bytes
+ * Per-lane sums in a fixed order, fixed trees inside a block, float64 partials per block reduced in block order by one
+ * workgroup; no float atomics: the same inputs, order and sizes give the same 18 x 8 bytes on every run. */
+size_t mvs_icp_step_workspace_bytes(int n_source);
+int mvs_icp_step_f32(const float* source, int n_source, const int* order, const double* T, const double* cp, const double* cq,
+                     float ox, float oy, float oz, float cell, int gx, int gy, int gz, int n_target,
+                     const void* target_workspace, size_t target_workspace_bytes, float max_corr_dist, double* moments,
+                     float* dist, int* index, void* workspace, size_t workspace_bytes, void* stream);
 /* Statistics of a distance array (inf = beyond):
  *   thresholds    [host] n_thresholds floats, each 0 < tau <= max_dist (MVS_E_BADARG otherwise); at most 16 (MVS_E_SHAPE)
  *   out           2 + n_thresholds doubles: sum of d over d < max_dist, count of d < max_dist, count of d < tau_t per threshold

@@ -115,6 +115,11 @@ SIGNATURES = {
     "mvs_nn_workspace_bytes": (_sz, [_i] * 5),
     "mvs_nn_f32": (_i, [_p, _i, _p, _i, _f, _f, _f, _f, _i, _i, _i, _f, _p, _p, _p, _sz, _p]),
     "mvs_nn_query_f32": (_i, [_i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "mvs_nn_target_workspace_bytes": (_sz, [_i] * 4),
+    "mvs_nn_target_build_f32": (_i, [_p, _i, _f, _f, _f, _f, _i, _i, _i, _p, _sz, _p]),
+    "mvs_icp_step_workspace_bytes": (_sz, [_i]),
+    "mvs_icp_step_f32": (_i, [_p, _i, _p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _f, _f, _f, _f,
+                              _i, _i, _i, _i, _p, _sz, _f, _p, _p, _p, _p, _sz, _p]),
     "mvs_dist_stats_workspace_bytes": (_sz, [_i, _i]),
     "mvs_dist_stats_f32": (_i, [_p, _i, _f, C.POINTER(C.c_float), _i, _p, _p, _sz, _p]),
     "mvs_voxel_keys_f32": (_i, [_p, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),

@@ -23,6 +23,11 @@
 //
 // Voxel downsampling (mvs_voxel_keys_f32, then a stable key sort by the caller, then mvs_voxel_select_f32): float64 keys,
 // "first of run" marks on the sorted keys set the keep flag of the run's first point in input order, ordered compaction.
+//
+// ICP registration (mvsnet_amd/register.py is normative): mvs_nn_target_build_f32 is count / scan / scatter for a target that
+// does not move, once; mvs_icp_step_f32 is one pass per iteration, one lane per source point: transform in float64, the
+// query above, the eighteen float64 moments of the correspondences, reduced as the statistics are.  Nothing per point
+// goes to memory unless the caller asks for dist / index.
 #include "common.h"
 
 namespace {
@@ -198,14 +203,11 @@ __device__ __forceinline__ void pc_visit_ball(const float4* __restrict__ ts, con
     }
 }
 
-__global__ __launch_bounds__(PC_THREADS) void pc_nn_query_kernel(
-        const float4* __restrict__ qs, int nq, const float4* __restrict__ ts, const int* __restrict__ tstart, float ox, float oy,
-        float oz, float cell, int gx, int gy, int gz, float max_dist, float* __restrict__ dist, int* __restrict__ index,
-        int* __restrict__ visited) {
-    const int i = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (i >= nq) return;
-    const float4 q = qs[i];
-    const int qi = __float_as_int(q.w);
+// The query loop: the nearest target point of q within max_dist -> best2 (float32 d^2, +inf when the grid's box is beyond
+// max_dist), bi (its input index), seen (candidates compared).  The caller applies the cap best2 <= max_dist^2.
+__device__ __forceinline__ void pc_query(const float4* __restrict__ ts, const int* __restrict__ tstart, float4 q, float ox,
+                                         float oy, float oz, float cell, int gx, int gy, int gz, float max_dist, float& best2,
+                                         int& bi, int& seen) {
     const int cx = pc_cell_axis(q.x, ox, cell, gx), cy = pc_cell_axis(q.y, oy, cell, gy), cz = pc_cell_axis(q.z, oz, cell, gz);
     const int gmax = max(gx, max(gy, gz));
     const float scale = fmaxf(fabsf(q.x), fmaxf(fabsf(q.y), fabsf(q.z))) + fmaxf(fabsf(ox), fmaxf(fabsf(oy), fabsf(oz))) +
@@ -215,8 +217,9 @@ __global__ __launch_bounds__(PC_THREADS) void pc_nn_query_kernel(
     // distance outside the grid's box per axis (every target point lies inside it)
     const float outx = pc_slab_gap(q.x, ox, hx, eps), outy = pc_slab_gap(q.y, oy, hy, eps), outz = pc_slab_gap(q.z, oz, hz, eps);
     const float md2 = max_dist * max_dist;
-    float best2 = __builtin_inff();
-    int bi = 0x7fffffff, seen = 0;
+    best2 = __builtin_inff();
+    bi = 0x7fffffff;
+    seen = 0;
     const float box2 = outx * outx + outy * outy + outz * outz;
     if (box2 * PC_SHRINK <= md2) {
         // the query's own cell first: a good first `best` prunes the rows of the first ball
@@ -230,7 +233,20 @@ __global__ __launch_bounds__(PC_THREADS) void pc_nn_query_kernel(
             if (last || best2 < inner * inner * PC_SHRINK) break;   // the nearest point lies inside the searched ball
         }
     }
-    const bool in = best2 <= md2;
+}
+
+__global__ __launch_bounds__(PC_THREADS) void pc_nn_query_kernel(
+        const float4* __restrict__ qs, int nq, const float4* __restrict__ ts, const int* __restrict__ tstart, float ox, float oy,
+        float oz, float cell, int gx, int gy, int gz, float max_dist, float* __restrict__ dist, int* __restrict__ index,
+        int* __restrict__ visited) {
+    const int i = blockIdx.x * PC_THREADS + threadIdx.x;
+    if (i >= nq) return;
+    const float4 q = qs[i];
+    const int qi = __float_as_int(q.w);
+    float best2;
+    int bi, seen;
+    pc_query(ts, tstart, q, ox, oy, oz, cell, gx, gy, gz, max_dist, best2, bi, seen);
+    const bool in = best2 <= max_dist * max_dist;
     dist[qi] = in ? sqrtf(best2) : __builtin_inff();
     index[qi] = in ? bi : -1;
     if (visited) visited[qi] = seen;
@@ -295,6 +311,81 @@ __global__ __launch_bounds__(PC_THREADS) void pc_stats_final_kernel(const double
         for (int b = threadIdx.x; b < nb; b += PC_THREADS) c += pcnt[(size_t)b * (1 + PC_MAX_THRESHOLDS) + k];
         const long long v = pc_block_sum(c, shl);
         if (threadIdx.x == 0) out[1 + k] = (double)v;
+    }
+}
+
+// ------------------------------------------------------------------ one ICP registration step (mvs_icp_step_f32)
+// moments = [count, sum |r|^2, sum a (3), sum b (3), sum a b^T (9, row-major), sum |a|^2] over the source points p that have
+// a target point q within max_corr_dist of fl32(T p): a = p - cp, b = q - cq, r = T p - q in float64 (T p unrounded).
+// mvsnet_amd/register.py is normative.
+
+constexpr int PC_ICP_MOMENTS = 18;
+constexpr int PC_ICP_BLOCKS = 2048;
+
+struct PcIcpParams { double T[12], cp[3], cq[3]; };
+
+// T[i,0] x + T[i,1] y + T[i,2] z + T[i,3], left to right, every product and sum rounded (no fused multiply-add), as
+// evaluate._transform evaluates it.
+__device__ __forceinline__ double pc_affine_row(const double* __restrict__ r, double x, double y, double z) {
+#pragma clang fp contract(off)
+    return ((x * r[0] + y * r[1]) + z * r[2]) + r[3];
+}
+
+// One lane per source point in processing order (order[i], or i): blocks sweep the cloud in strides of the grid, so lane L of
+// the grid sums points L, L + lanes, ... in that order.  tpos: the target's per-point cell and rank, which with tstart give
+// the position of target point j in the cell-ordered copy.  partial: PC_ICP_MOMENTS doubles per block.
+__global__ __launch_bounds__(PC_THREADS) void pc_icp_step_kernel(
+        const float* __restrict__ src, int n, const int* __restrict__ order, PcIcpParams P, const float4* __restrict__ ts,
+        const int* __restrict__ tstart, const int* __restrict__ tcell, const int* __restrict__ trank, float ox, float oy, float oz,
+        float cell, int gx, int gy, int gz, float max_dist, double* __restrict__ partial, float* __restrict__ dist,
+        int* __restrict__ index) {
+    __shared__ double shd[PC_THREADS / 64];
+    double m[PC_ICP_MOMENTS];
+#pragma unroll
+    for (int k = 0; k < PC_ICP_MOMENTS; ++k) m[k] = 0.0;
+    for (long long i = (long long)blockIdx.x * PC_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * PC_THREADS) {
+        const int s = order ? order[i] : (int)i;
+        if (s < 0 || s >= n) continue;                       // not a permutation: the point is left out, nothing is read
+        const double px = (double)src[3 * (size_t)s], py = (double)src[3 * (size_t)s + 1], pz = (double)src[3 * (size_t)s + 2];
+        const double tx = pc_affine_row(P.T, px, py, pz), ty = pc_affine_row(P.T + 4, px, py, pz),
+                     tz = pc_affine_row(P.T + 8, px, py, pz);
+        const float4 q = make_float4((float)tx, (float)ty, (float)tz, 0.f);
+        float best2;
+        int bi, seen;
+        pc_query(ts, tstart, q, ox, oy, oz, cell, gx, gy, gz, max_dist, best2, bi, seen);
+        const bool in = best2 <= max_dist * max_dist;
+        if (dist) dist[s] = in ? sqrtf(best2) : __builtin_inff();
+        if (index) index[s] = in ? bi : -1;
+        if (!in) continue;
+        const float4 t = ts[tstart[tcell[bi]] + trank[bi]];
+        const double a0 = px - P.cp[0], a1 = py - P.cp[1], a2 = pz - P.cp[2];
+        const double b0 = (double)t.x - P.cq[0], b1 = (double)t.y - P.cq[1], b2 = (double)t.z - P.cq[2];
+        const double r0 = tx - (double)t.x, r1 = ty - (double)t.y, r2 = tz - (double)t.z;
+        m[0] += 1.0;
+        m[1] += (r0 * r0 + r1 * r1) + r2 * r2;
+        m[2] += a0;  m[3] += a1;  m[4] += a2;
+        m[5] += b0;  m[6] += b1;  m[7] += b2;
+        m[8] += a0 * b0;   m[9] += a0 * b1;   m[10] += a0 * b2;
+        m[11] += a1 * b0;  m[12] += a1 * b1;  m[13] += a1 * b2;
+        m[14] += a2 * b0;  m[15] += a2 * b1;  m[16] += a2 * b2;
+        m[17] += (a0 * a0 + a1 * a1) + a2 * a2;
+    }
+#pragma unroll
+    for (int k = 0; k < PC_ICP_MOMENTS; ++k) {
+        const double v = pc_block_sum(m[k], shd);
+        if (threadIdx.x == 0) partial[(size_t)blockIdx.x * PC_ICP_MOMENTS + k] = v;
+    }
+}
+
+// One workgroup: the nb partials in block order.
+__global__ __launch_bounds__(PC_THREADS) void pc_icp_final_kernel(const double* __restrict__ partial, int nb,
+                                                                   double* __restrict__ out) {
+    __shared__ double shd[PC_THREADS / 64];
+    for (int k = 0; k < PC_ICP_MOMENTS; ++k) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < nb; b += PC_THREADS) s += partial[(size_t)b * PC_ICP_MOMENTS + k];
+        const double total = pc_block_sum(s, shd);
+        if (threadIdx.x == 0) out[k] = total;
     }
 }
 
@@ -408,6 +499,26 @@ size_t voxel_select_bytes(int n) {
     return pc_align((size_t)n) + pc_align(((size_t)nb + 1) * sizeof(int)) + pc_align(((size_t)pc_scan_chunks(nb + 1) + 1) * sizeof(int));
 }
 
+// The target alone: per-cell starts, scan scratch, per-point cell and rank (kept: they locate a point in the sorted copy), sorted copy.
+struct TargetLayout { size_t starts, bsum, tcell, trank, tsorted, total; };
+
+TargetLayout target_layout(int nt, long long ncell) {
+    TargetLayout L{};
+    const long long m = ncell + 1;
+    size_t o = 0;
+    L.starts = o;  o += pc_align((size_t)m * sizeof(int));
+    L.bsum = o;    o += pc_align(((size_t)pc_scan_chunks(m) + 1) * sizeof(int));
+    L.tcell = o;   o += pc_align((size_t)nt * sizeof(int));
+    L.trank = o;   o += pc_align((size_t)nt * sizeof(int));
+    L.tsorted = o; o += pc_align((size_t)nt * sizeof(float4));
+    L.total = o;
+    return L;
+}
+
+int icp_blocks(int n) { return (int)std::min<long long>(PC_ICP_BLOCKS, ((long long)n + PC_THREADS - 1) / PC_THREADS); }
+
+size_t icp_bytes(int n) { return pc_align((size_t)icp_blocks(n) * PC_ICP_MOMENTS * sizeof(double)); }
+
 }  // namespace
 
 extern "C" size_t mvs_nn_workspace_bytes(int n_query, int n_target, int gx, int gy, int gz) {
@@ -468,6 +579,75 @@ extern "C" int mvs_nn_query_f32(int n_query, int n_target, float ox, float oy, f
     hipLaunchKernelGGL(pc_nn_query_kernel, dim3(mvs_cdiv(n_query, PC_THREADS)), dim3(PC_THREADS), 0, mvs_stream(stream),
                        reinterpret_cast<const float4*>(ws + L.qsorted), n_query, reinterpret_cast<const float4*>(ws + L.tsorted),
                        reinterpret_cast<const int*>(ws + L.starts), ox, oy, oz, cell, gx, gy, gz, max_dist, dist, index, visited);
+    MVS_LAUNCH_RET();
+}
+
+extern "C" size_t mvs_nn_target_workspace_bytes(int n_target, int gx, int gy, int gz) {
+    if (n_target <= 0 || !nn_grid_ok(gx, gy, gz)) return 0;
+    return target_layout(n_target, (long long)gx * gy * gz).total;
+}
+
+extern "C" int mvs_nn_target_build_f32(const float* target, int n_target, float ox, float oy, float oz, float cell, int gx, int gy,
+                                       int gz, void* workspace, size_t workspace_bytes, void* stream) {
+    MVS_CHECK_ARG(target && workspace && n_target > 0 && gx > 0 && gy > 0 && gz > 0);
+    MVS_CHECK_ARG(__builtin_isfinite(ox) && __builtin_isfinite(oy) && __builtin_isfinite(oz));
+    MVS_CHECK_ARG(cell > 0.f && __builtin_isfinite(cell));
+    if (!nn_grid_ok(gx, gy, gz)) return MVS_E_SHAPE;
+    const long long ncell = (long long)gx * gy * gz;
+    const TargetLayout L = target_layout(n_target, ncell);
+    if (workspace_bytes < L.total) return MVS_E_WORKSPACE;
+    hipStream_t st = mvs_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    int* tstart = reinterpret_cast<int*>(ws + L.starts);
+    int* tcell = reinterpret_cast<int*>(ws + L.tcell);
+    int* trank = reinterpret_cast<int*>(ws + L.trank);
+    hipError_t e = hipMemsetAsync(tstart, 0, (size_t)(ncell + 1) * sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pc_cell_count_kernel, dim3(mvs_cdiv(n_target, PC_THREADS)), dim3(PC_THREADS), 0, st, target, n_target,
+                       ox, oy, oz, cell, gx, gy, gz, tcell, trank, tstart);
+    e = pc_scan(tstart, ncell + 1, 0, 1, reinterpret_cast<int*>(ws + L.bsum), st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pc_scatter_kernel, dim3(mvs_cdiv(n_target, PC_THREADS)), dim3(PC_THREADS), 0, st, target, n_target,
+                       tcell, trank, tstart, reinterpret_cast<float4*>(ws + L.tsorted));
+    MVS_LAUNCH_RET();
+}
+
+extern "C" size_t mvs_icp_step_workspace_bytes(int n_source) {
+    return n_source > 0 ? icp_bytes(n_source) : 0;
+}
+
+extern "C" int mvs_icp_step_f32(const float* source, int n_source, const int* order, const double* T, const double* cp,
+                                const double* cq, float ox, float oy, float oz, float cell, int gx, int gy, int gz, int n_target,
+                                const void* target_workspace, size_t target_workspace_bytes, float max_corr_dist,
+                                double* moments, float* dist, int* index, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    MVS_CHECK_ARG(source && T && cp && cq && target_workspace && moments && workspace);
+    MVS_CHECK_ARG(n_source > 0 && n_target > 0 && gx > 0 && gy > 0 && gz > 0);
+    MVS_CHECK_ARG(__builtin_isfinite(ox) && __builtin_isfinite(oy) && __builtin_isfinite(oz));
+    MVS_CHECK_ARG(cell > 0.f && __builtin_isfinite(cell));
+    MVS_CHECK_ARG(max_corr_dist > 0.f && __builtin_isfinite(max_corr_dist * max_corr_dist));
+    PcIcpParams P;
+    for (int k = 0; k < 12; ++k) {
+        MVS_CHECK_ARG(__builtin_isfinite(T[k]));
+        P.T[k] = T[k];
+    }
+    for (int k = 0; k < 3; ++k) {
+        MVS_CHECK_ARG(__builtin_isfinite(cp[k]) && __builtin_isfinite(cq[k]));
+        P.cp[k] = cp[k];
+        P.cq[k] = cq[k];
+    }
+    if (!nn_grid_ok(gx, gy, gz)) return MVS_E_SHAPE;
+    const TargetLayout L = target_layout(n_target, (long long)gx * gy * gz);
+    if (target_workspace_bytes < L.total || workspace_bytes < icp_bytes(n_source)) return MVS_E_WORKSPACE;
+    hipStream_t st = mvs_stream(stream);
+    const char* tw = static_cast<const char*>(target_workspace);
+    double* partial = static_cast<double*>(workspace);
+    const int nb = icp_blocks(n_source);
+    hipLaunchKernelGGL(pc_icp_step_kernel, dim3(nb), dim3(PC_THREADS), 0, st, source, n_source, order, P,
+                       reinterpret_cast<const float4*>(tw + L.tsorted), reinterpret_cast<const int*>(tw + L.starts),
+                       reinterpret_cast<const int*>(tw + L.tcell), reinterpret_cast<const int*>(tw + L.trank), ox, oy, oz, cell,
+                       gx, gy, gz, max_corr_dist, partial, dist, index);
+    hipLaunchKernelGGL(pc_icp_final_kernel, dim3(1), dim3(PC_THREADS), 0, st, partial, nb, moments);
     MVS_LAUNCH_RET();
 }
 

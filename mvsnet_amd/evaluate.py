@@ -2,7 +2,7 @@
 
     python -m mvsnet_amd.evaluate --pred P.ply --gt G.ply --max_dist 20 [--thresholds 0.5,1,2]
         [--crop x0,y0,z0,x1,y1,z1] [--transform T.txt] [--voxel_pred s] [--voxel_gt s] [--out metrics.json]
-        [--dump_distances DIR]
+        [--dump_distances DIR] [--align icp --align_stages 4:8:30,2:4:30,0:2:30 [--align_with_scale]]
 
 The nearest-neighbour searches, the voxel downsampling and the statistics are HIP kernels (csrc/pointcloud.hip); torch owns
 the device memory, the stable key sort of the downsampling and the transform / crop arithmetic.
@@ -18,6 +18,11 @@ truth, each (n,3) float32.
        kept point of each occupied voxel is the FIRST point in input order (not a mean), and the output stays in input
        order (np.unique(keys, axis=0, return_index=True), sorted).
     A cloud that is empty after preprocessing is a ValueError that names it.
+  * Alignment (align, optional; off by default and then nothing here changes).  Before the preprocessing, P is registered to
+    G by ICP (mvsnet_amd/register.py, register_point_clouds with the options of `align`), starting from `transform` (identity
+    without one) and restricted to `crop`; the refined transform then takes the place of `transform` in step 1, and the
+    metrics gain "alignment": the transform, every stage's fitness / inlier_rmse / iterations and the reason the last stage
+    stopped.
   * Nearest neighbour of a query cloud A in a target cloud B: d(a) = min_b |a - b| when that minimum is <= max_dist, else
     +inf ("beyond"); nn(a) is the minimiser's index in B, or -1 when beyond.  On the device d^2 is computed in float32 from
     float32 differences, and exact ties of that d^2 go to the smallest index.
@@ -389,11 +394,21 @@ class EvaluationPlan:
     current stream (capturable); ``result()`` synchronises once and returns the metrics dict of evaluate_point_clouds."""
 
     def __init__(self, pred, gt, *, max_dist, thresholds=(), transform=None, crop=None, voxel_pred=0.0, voxel_gt=0.0,
-                 device=None):
+                 align=None, device=None):
         import torch
         from . import _lib
         self.max_dist, self.thresholds = check_thresholds(thresholds, max_dist)
         self.pred_points, self.gt_points = len(pred), len(gt)
+        self.alignment = None
+        if align is not None:
+            from . import register
+            if transform is not None:
+                check_transform(transform)
+            reg = register.register_point_clouds(pred, gt, init=transform, crop=crop, device=device, **dict(align))
+            transform = reg["transform"]
+            self.alignment = {"transform": reg["transform"], "stopped": reg["stopped"],
+                              "stages": [{k: st[k] for k in ("voxel", "max_corr_dist", "fitness", "inlier_rmse", "iterations",
+                                                             "stopped")} for st in reg["stages"]]}
         p, g = preprocess(pred, gt, transform=transform, crop=crop, voxel_pred=voxel_pred, voxel_gt=voxel_gt, device=device)
         self.dev = p.device
         self.acc = NearestPlan(p, g, self.max_dist, device=self.dev)
@@ -443,16 +458,19 @@ class EvaluationPlan:
         out.update({"max_dist": self.max_dist, "pred_points": self.pred_points, "gt_points": self.gt_points,
                     "pred_points_used": len(dp), "gt_points_used": len(dg),
                     "grid_pred_to_gt": self.acc.grid, "grid_gt_to_pred": self.comp.grid})
+        if self.alignment is not None:
+            out["alignment"] = self.alignment
         return out
 
 
 def evaluate_point_clouds(pred, gt, *, max_dist, thresholds=(), transform=None, crop=None, voxel_pred=0.0, voxel_gt=0.0,
-                          device=None):
+                          align=None, device=None):
     """Accuracy / completeness / precision / recall / F-score of pred against gt (numpy arrays or device tensors (n,3)) on
     the GPU; semantics in the module docstring.  Returns the metrics dict (plus the point counts before and after the
-    preprocessing and the two grids that were used)."""
+    preprocessing and the two grids that were used).  align: None, or a dict of register_point_clouds options (at least
+    "stages") to refine `transform` by ICP first."""
     plan = EvaluationPlan(pred, gt, max_dist=max_dist, thresholds=thresholds, transform=transform, crop=crop,
-                          voxel_pred=voxel_pred, voxel_gt=voxel_gt, device=device)
+                          voxel_pred=voxel_pred, voxel_gt=voxel_gt, align=align, device=device)
     plan.enqueue()
     return plan.result()
 
@@ -478,7 +496,21 @@ def main(argv=None):
     ap.add_argument("--voxel_gt", type=float, default=0.0)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--dump_distances", default=None, help="directory for pred_to_gt.npy and gt_to_pred.npy")
+    ap.add_argument("--align", default=None, choices=["icp"], help="refine --transform (or identity) by ICP before evaluating")
+    ap.add_argument("--align_stages", default=None, help="voxel:max_corr_dist:max_iterations[,...] (mvsnet_amd.register)")
+    ap.add_argument("--align_with_scale", action="store_true", help="let the alignment solve for a uniform scale as well")
     a = ap.parse_args(argv)
+    align = None
+    if a.align:
+        from . import register
+        if not a.align_stages:
+            raise SystemExit("mvsnet_amd.evaluate: --align icp needs --align_stages")
+        try:
+            align = {"stages": register.parse_stages(a.align_stages), "with_scale": a.align_with_scale}
+        except ValueError as e:
+            raise SystemExit("mvsnet_amd.evaluate: %s" % e)
+    elif a.align_stages or a.align_with_scale:
+        raise SystemExit("mvsnet_amd.evaluate: --align_stages / --align_with_scale need --align icp")
     from .depthfusion import _gpu_ready
     why = _gpu_ready()
     if why is not None:
@@ -490,7 +522,7 @@ def main(argv=None):
     gt, _ = read_ply_points(a.gt)
     try:
         plan = EvaluationPlan(pred, gt, max_dist=a.max_dist, thresholds=thresholds, transform=transform, crop=crop,
-                              voxel_pred=a.voxel_pred, voxel_gt=a.voxel_gt)
+                              voxel_pred=a.voxel_pred, voxel_gt=a.voxel_gt, align=align)
     except ValueError as e:
         raise SystemExit("mvsnet_amd.evaluate: %s" % e)
     plan.enqueue()
