@@ -695,6 +695,28 @@ size_t mvs_voxel_select_workspace_bytes(int n);
 int mvs_voxel_select_f32(const float* xyz, int n, const long long* sorted_keys, const long long* order, float* out, int* count,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Rendering of a point cloud into per-view depth maps with a z-buffer (csrc/render.hip; semantics in mvsnet_amd/render.py):
+ *   xyz           (n,3) float32, read only; non-finite coordinates are allowed (such a point covers no pixel)
+ *   order         NULL or (n) int32, a permutation of the points: the order in which lanes take them (points that fall on
+ *                 neighbouring pixels side by side run faster); NULL = input order.  It never changes a byte of the output
+ *   proj          [device] V*12 floats: P_v = K_v [R_v | t_v] (3x4, row-major) at [v*12], composed in float64, rounded once
+ *   splat         s in 0..32: a point covers the (2 s + 1)^2 pixels around its own, clipped to the image
+ *   min_depth     >= 0, finite: a point is a candidate in a view only when its depth w > min_depth
+ *   occl_radius   0: no hidden-point removal.  k in 1..16: a pixel of raw depth z > 0 is removed when at least occl_count
+ *                 (>= 1) other pixels q of its (2 k + 1)^2 window have 0 < raw[q] < z * occl_ratio (0 < occl_ratio < 1)
+ *   depth         (V,H,W) float32: per pixel the smallest w of the points that cover it, 0 where empty (or removed)
+ *   index         NULL or (V,H,W) int32: the input index of that point (exact ties of w: the smallest), -1 where empty
+ *   workspace     mvs_render_workspace_bytes(V, H, W, occlusion) bytes (0 for invalid sizes): the 8-byte keys
+ *                 bits(w) << 32 | index of all pixels, which the call clears itself, plus the raw map when occlusion != 0
+ * Only enqueues on `stream`: nothing is allocated, nothing synchronised.  The only atomics are 64-bit unsigned minima, so
+ * the same inputs give the same bytes in any order and grid.  Every argument is checked before the first GPU call:
+ * MVS_E_BADARG for a null pointer or an option outside the ranges above, MVS_E_SHAPE when V*H*W exceeds 2^31-1 or H or W
+ * exceeds 2^24 (pixel coordinates are compared as float32), MVS_E_WORKSPACE. */
+size_t mvs_render_workspace_bytes(int V, int H, int W, int occlusion);
+int mvs_render_points_f32(const float* xyz, int n, const int* order, const float* proj, int V, int H, int W, int splat,
+                          float min_depth, int occl_radius, float occl_ratio, int occl_count, float* depth, int* index,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,8 @@ SIGNATURES = {
     "mvs_voxel_keys_f32": (_i, [_p, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
     "mvs_voxel_select_workspace_bytes": (_sz, [_i]),
     "mvs_voxel_select_f32": (_i, [_p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "mvs_render_workspace_bytes": (_sz, [_i] * 4),
+    "mvs_render_points_f32": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _f, _i, _f, _i, _p, _p, _p, _sz, _p]),
 }
 
 CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}
