@@ -717,6 +717,44 @@ int mvs_render_points_f32(const float* xyz, int n, const int* order, const float
                           float min_depth, int occl_radius, float occl_ratio, int occl_count, float* depth, int* index,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* View selection from cameras and a cloud (csrc/view_selection.hip; semantics in mvsnet_amd/select_views.py).  Common to the
+ * three calls:
+ *   xyz           (n,3) float32, read only; non-finite coordinates are allowed
+ *   mask          (n, mask_words) 64-bit words, mask_words >= ceil(V / 64): view position p of point i is bit p % 64 of word
+ *                 p / 64 of row i.  Bits at positions >= V are ignored by the readers
+ *   proj          [device] 12 floats per view, as mvs_render_points_f32 takes them
+ * mvs_view_visibility_f32: the V views of one size H x W; sets, never clears, the bit view_bits[v] of every point visible
+ * in view v (the caller zeroes the mask before the first call; a view_bits entry outside 0 .. 64 mask_words - 1 is left out).
+ *   view_bits     [device] (V) int32: the bit position of each of the call's views
+ *   min_depth     >= 0, finite: visible only when w > min_depth
+ *   zbuf          NULL (frustum) or (V,H,W) float32 depth maps of the call's views: visible only when the map is > 0 at the
+ *                 point's pixel and w <= map * z_tol (z_tol >= 1, a float32 product)
+ * mvs_view_scores_f32: over all pairs a < b < V of view positions, shared[a V + b] = the number of points with both bits set
+ * and score_sum[a V + b] = the sum of table[k] over them (select_views.py, "pair score"); both (V,V) int64, cleared by the
+ * call, entries with a >= b stay 0.
+ *   order         NULL or (n) int32, a permutation of the points: which lane takes which point, never an output byte
+ *   centres       [device] (V,3) float32 camera centres by view position
+ *   table         [device] 8192 uint16 weights
+ *   workspace     mvs_view_scores_workspace_bytes(n, V) bytes (0 for invalid sizes): the work counters, cleared by the call
+ * mvs_view_depth_hist_f32: histograms of the float32 bits of w = row 2 of proj[v] applied to the point, over the points with
+ * bit v set; proj holds all V views by position.  The call clears hist.
+ *   pass 0        prefixes NULL; hist (V, 65536) uint32 counts of bits(w) >> 16
+ *   pass 1        prefixes [device] (V,2) int32; hist (V, 2, 65536) uint32: hist[v][j] counts bits(w) & 0xffff over the points
+ *                 with bits(w) >> 16 == prefixes[v][j]
+ * All three only enqueue on `stream`: nothing is allocated, nothing synchronised, and every accumulation is an integer, so
+ * the same inputs give the same bytes in any order and grid.  Every argument is checked before the first GPU call:
+ * MVS_E_BADARG for a null pointer or an option outside the ranges above, MVS_E_SHAPE for V > 512, n < 1,
+ * mask_words < ceil(V / 64), H or W beyond 2^24 or V*H*W beyond 2^31-1, MVS_E_WORKSPACE. */
+int mvs_view_visibility_f32(const float* xyz, int n, const float* proj, const int* view_bits, int V, int H, int W,
+                            float min_depth, const float* zbuf, float z_tol, unsigned long long* mask, int mask_words,
+                            void* stream);
+size_t mvs_view_scores_workspace_bytes(int n, int V);
+int mvs_view_scores_f32(const float* xyz, int n, const int* order, const unsigned long long* mask, int mask_words,
+                        const float* centres, int V, const unsigned short* table, long long* score_sum, long long* shared,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int mvs_view_depth_hist_f32(const float* xyz, int n, const float* proj, int V, const unsigned long long* mask, int mask_words,
+                            int pass, const int* prefixes, unsigned int* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,10 @@ SIGNATURES = {
     "mvs_voxel_select_f32": (_i, [_p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "mvs_render_workspace_bytes": (_sz, [_i] * 4),
     "mvs_render_points_f32": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _f, _i, _f, _i, _p, _p, _p, _sz, _p]),
+    "mvs_view_visibility_f32": (_i, [_p, _i, _p, _p, _i, _i, _i, _f, _p, _f, _p, _i, _p]),
+    "mvs_view_scores_workspace_bytes": (_sz, [_i, _i]),
+    "mvs_view_scores_f32": (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    "mvs_view_depth_hist_f32": (_i, [_p, _i, _p, _i, _p, _i, _i, _p, _p, _p]),
 }
 
 CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}

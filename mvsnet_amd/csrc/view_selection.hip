@@ -1,0 +1,352 @@
+// View selection from cameras and a cloud (mvs_view_visibility_f32, mvs_view_scores_f32, mvs_view_depth_hist_f32).  The
+// semantics are normative in mvsnet_amd/select_views.py; tests/view_selection_reference.py restates them in numpy.
+//
+//   visibility  one lane per point, the view loop inside the lane with P_v's twelve floats in scalar registers: render.hip's
+//               float32 projection and pixel, the candidate test, optionally the comparison with a rendered depth map, and
+//               the point's bit of each view.  A lane owns its point's mask words, so it gathers the bits of one word in a
+//               register and ORs the word into memory when the next view falls into another word: no atomics.
+//   scores      the pair matrix is cut into tiles of 64 x 64 views, one tile per pair (wi <= wj) of mask words, so a tile's
+//               views are one word (diagonal tile) or two (off-diagonal tile) of a point's mask.  A workgroup owns one tile
+//               as 64-bit accumulators in LDS (count << 40 | sum of weights) beside the 16 KB weight table; its waves take
+//               chunks of VS_CHUNK points from the tile's counter in the workspace.  Per point the wave compacts the tile's
+//               visible views out of the mask words (lane l is view l of the word; its camera centre stays in registers),
+//               stages c_v - p and its squared norm in LDS at the view's rank, and the lanes take the pairs of the list(s)
+//               in strides of 64: k, T[k] from LDS, one LDS atomic add.  At the end the tile goes to score_sum and shared
+//               with 64-bit integer atomics.  Integer sums only: any order gives the same bytes.
+//               A launch takes at most VS_SEGMENT = 2^23 points, so a count stays below 2^24 and a sum below 2^39 whatever
+//               share of the points one workgroup ends up with; a larger cloud is a loop of launches on the host side.
+//   depth hist  pass 0: a workgroup per (share of the points, view) counts bits(w) >> 16 of the points with the view's bit set
+//               in a 128 KB histogram in LDS and adds its non-zero bins to the view's histogram in memory; a scene's depths
+//               fall into a few dozen of these bins, and global atomics on them would serialise.  Pass 1: one lane per
+//               point, per view with the point's bit set and a high half equal to one of the view's two prefixes an integer
+//               atomic add into the histogram of bits(w) & 0xffff: few points, spread over 65 536 bins.
+#include "common.h"
+
+namespace {
+
+constexpr int VS_MAX_VIEWS = 512;
+constexpr int VS_THREADS = 256;                 // visibility and histogram kernels
+constexpr int VS_BLOCKS = 2048;
+constexpr int VS_MAX_AXIS = 1 << 24;            // H, W: every pixel coordinate is an exact float32
+constexpr int VS_TABLE = 8192;                  // entries of the weight table
+constexpr int VS_WAVES = 6;                     // waves of a score workgroup: 16 KB table + 32 KB tile + 6 x 2.1 KB lists < 64 KB
+constexpr int VS_SCORE_THREADS = VS_WAVES * MVS_WAVE;
+constexpr int VS_CHUNK = 32;                    // points a wave takes from the counter at a time
+constexpr int VS_SEGMENT = 1 << 23;             // points per launch of the score kernel
+constexpr int VS_SCORE_BLOCKS = 512;            // two resident workgroups on each of the 256 CUs
+constexpr int VS_COUNT_SHIFT = 40;
+constexpr int VS_BINS = 65536;
+constexpr int VS_LDS_BINS = 32768;              // pass 0 in LDS: the high halves of all non-negative floats, 128 KB of the CU's 160
+constexpr int VS_HIST_THREADS = 1024;
+constexpr int VS_HIST_BLOCKS = 768;             // three rounds of one workgroup per CU
+
+__device__ __forceinline__ float vs_row(const float* __restrict__ r, float x, float y, float z) {
+#pragma clang fp contract(off)
+    return ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
+}
+
+__device__ __forceinline__ float vs_pixel(float a, float b) {
+#pragma clang fp contract(off)
+    return floorf(__fdiv_rn(a, b) + 0.5f);
+}
+
+// (x*x' + y*y') + z*z', every product and sum rounded
+__device__ __forceinline__ float vs_dot(float ax, float ay, float az, float bx, float by, float bz) {
+#pragma clang fp contract(off)
+    return (ax * bx + ay * by) + az * bz;
+}
+
+__device__ __forceinline__ unsigned long long vs_valid_bits(int word, int V) {
+    const int left = V - 64 * word;
+    return left >= 64 ? ~0ull : left <= 0 ? 0ull : (1ull << left) - 1ull;
+}
+
+__global__ __launch_bounds__(VS_THREADS) void vs_visibility_kernel(const float* __restrict__ xyz, int n, const float* __restrict__ proj,
+                                                                    const int* __restrict__ view_bits, int V, int H, int W,
+                                                                    float min_depth, const float* __restrict__ zbuf, float z_tol,
+                                                                    unsigned long long* __restrict__ mask, int mask_words) {
+#pragma clang fp contract(off)
+    const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+    const size_t plane = (size_t)H * W;
+    for (long long i = (long long)blockIdx.x * VS_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * VS_THREADS) {
+        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        unsigned long long* __restrict__ row = mask + (size_t)i * mask_words;
+        int word = -1;                                               // wave-uniform, as the views are
+        unsigned long long bits = 0;
+        for (int v = 0; v < V; ++v) {
+            const float* __restrict__ P = proj + 12 * (size_t)v;
+            const int bit = view_bits[v];
+            if (bit < 0 || bit >= 64 * mask_words) continue;         // no such bit in the mask: the view is left out
+            if ((bit >> 6) != word) {
+                if (bits) row[word] |= bits;
+                word = bit >> 6;
+                bits = 0;
+            }
+            const float w = vs_row(P + 8, x, y, z);
+            const float fx = vs_pixel(vs_row(P, x, y, z), w), fy = vs_pixel(vs_row(P + 4, x, y, z), w);
+            bool vis = __builtin_isfinite(w) && w > min_depth && __builtin_isfinite(fx) && __builtin_isfinite(fy) &&
+                       fx >= 0.f && fx <= wmax && fy >= 0.f && fy <= hmax;
+            if (zbuf && vis) {                                       // inside the image: the conversion is exact
+                const float zb = zbuf[(size_t)v * plane + (size_t)(int)fy * W + (int)fx];
+                vis = zb > 0.f && w <= zb * z_tol;
+            }
+            bits |= vis ? 1ull << (bit & 63) : 0ull;
+        }
+        if (bits) row[word] |= bits;
+    }
+}
+
+// One staged view of a point: c_v - p and its squared norm.
+struct VsEntry { float x, y, z, nn; };
+
+struct VsLists {
+    VsEntry a[MVS_WAVE], b[MVS_WAVE];
+    unsigned char ia[MVS_WAVE], ib[MVS_WAVE];                       // the view's position inside its word
+};
+
+__device__ __forceinline__ unsigned long long vs_pair_term(const VsEntry& A, const VsEntry& B, const unsigned short* __restrict__ table) {
+#pragma clang fp contract(off)
+    const float dot = vs_dot(A.x, A.y, A.z, B.x, B.y, B.z);
+    const float r = __fdiv_rn(dot * dot, A.nn * B.nn);               // cos^2
+    float xx = 1.0f - r;
+    xx = xx < 0.f ? 0.f : xx;
+    // sqrtf, not __fsqrt_rn: the intrinsic compiles to the bare v_sqrt_f32 (1 ulp), sqrtf to the correctly rounded sequence
+    const float f = floorf(sqrtf(xx) * 8192.0f);                     // sin * 8192
+    unsigned t = 0;
+    if (dot > 0.f && __builtin_isfinite(f)) t = table[min(VS_TABLE - 1, (int)f)];
+    return (1ull << VS_COUNT_SHIFT) | t;
+}
+
+// grid: tiles x blocks per tile.  Points first .. first + count - 1 of the processing order.
+__global__ __launch_bounds__(VS_SCORE_THREADS) void vs_score_kernel(const float* __restrict__ xyz, int n, int first, int count,
+                                                                     const int* __restrict__ order,
+                                                                     const unsigned long long* __restrict__ mask, int mask_words,
+                                                                     const float* __restrict__ centres, int V,
+                                                                     const unsigned short* __restrict__ table_g, int blocks_per_tile,
+                                                                     unsigned int* __restrict__ counters,
+                                                                     unsigned long long* __restrict__ score_sum,
+                                                                     unsigned long long* __restrict__ shared_n) {
+#pragma clang fp contract(off)
+    __shared__ unsigned long long acc[MVS_WAVE * MVS_WAVE];
+    __shared__ unsigned short table[VS_TABLE];
+    __shared__ VsLists lists[VS_WAVES];
+
+    const int tile = blockIdx.x / blocks_per_tile;
+    int wi = 0, wj = tile;                                           // tile -> (wi <= wj), rows of the upper triangle in turn
+    for (int words = (V + 63) >> 6, len = words; wj >= len; wj -= len, --len) ++wi;
+    wj += wi;
+    const bool diag = wi == wj;
+    const unsigned long long valid_i = vs_valid_bits(wi, V), valid_j = vs_valid_bits(wj, V);
+
+    for (int e = threadIdx.x; e < MVS_WAVE * MVS_WAVE; e += VS_SCORE_THREADS) acc[e] = 0;
+    for (int e = threadIdx.x; e < VS_TABLE; e += VS_SCORE_THREADS) table[e] = table_g[e];
+    __syncthreads();
+
+    const int lane = threadIdx.x & (MVS_WAVE - 1), wave = threadIdx.x / MVS_WAVE;
+    VsLists& L = lists[wave];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // lane l is view l of either word: its camera centres stay in registers (views past V are never visible)
+    const int va = min(wi * 64 + lane, V - 1), vb = min(wj * 64 + lane, V - 1);
+    const float cax = centres[3 * va], cay = centres[3 * va + 1], caz = centres[3 * va + 2];
+    const float cbx = centres[3 * vb], cby = centres[3 * vb + 1], cbz = centres[3 * vb + 2];
+
+    for (;;) {
+        unsigned start = 0;
+        if (lane == 0) start = atomicAdd(counters + tile, (unsigned)VS_CHUNK);
+        start = __builtin_amdgcn_readfirstlane(start);
+        if (start >= (unsigned)count) break;
+        // lane l < VS_CHUNK fetches point l of the chunk; the point loop below reads them lane by lane
+        unsigned long long my_i = 0, my_j = 0;
+        float my_x = 0.f, my_y = 0.f, my_z = 0.f;
+        if (lane < VS_CHUNK && start + lane < (unsigned)count) {
+            const int at = first + (int)start + lane;
+            const int s = order ? order[at] : at;
+            if (s >= 0 && s < n) {                                   // not a permutation: the point is left out, nothing is read
+                my_i = mask[(size_t)s * mask_words + wi] & valid_i;
+                my_j = mask[(size_t)s * mask_words + wj] & valid_j;
+                my_x = xyz[3 * (size_t)s], my_y = xyz[3 * (size_t)s + 1], my_z = xyz[3 * (size_t)s + 2];
+            }
+        }
+        for (int p = 0; p < VS_CHUNK; ++p) {
+            const unsigned long long mi = __shfl(my_i, p, MVS_WAVE), mj = __shfl(my_j, p, MVS_WAVE);
+            const int ma = __popcll(mi), mb = __popcll(mj);
+            if (diag ? ma < 2 : (ma == 0 || mb == 0)) continue;      // wave-uniform
+            const float px = __shfl(my_x, p, MVS_WAVE), py = __shfl(my_y, p, MVS_WAVE), pz = __shfl(my_z, p, MVS_WAVE);
+            if ((mi >> lane) & 1ull) {
+                VsEntry e;
+                e.x = cax - px, e.y = cay - py, e.z = caz - pz;
+                e.nn = vs_dot(e.x, e.y, e.z, e.x, e.y, e.z);
+                const int rank = __popcll(mi & below);
+                L.a[rank] = e;
+                L.ia[rank] = (unsigned char)lane;
+            }
+            if (!diag && ((mj >> lane) & 1ull)) {
+                VsEntry e;
+                e.x = cbx - px, e.y = cby - py, e.z = cbz - pz;
+                e.nn = vs_dot(e.x, e.y, e.z, e.x, e.y, e.z);
+                const int rank = __popcll(mj & below);
+                L.b[rank] = e;
+                L.ib[rank] = (unsigned char)lane;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (diag) {
+                // round-robin pairing of M = ma | 1 entries (one absent when ma is even): row i meets (i + 1 + c) mod M for
+                // c < M / 2, which names every unordered pair exactly once
+                const int M = ma | 1, half = M >> 1, total = M * half;
+                const float inv = 1.0f / (float)half;
+                for (int q = lane; q < total; q += MVS_WAVE) {
+                    const int i = (int)(((float)q + 0.5f) * inv);    // q / half: q < 2080, exact
+                    int j = i + 1 + (q - i * half);
+                    j -= j >= M ? M : 0;
+                    if (i >= ma || j >= ma) continue;
+                    const int lo = min(i, j), hi = max(i, j);        // ranks ascend with the views
+                    atomicAdd(&acc[(int)L.ia[lo] * MVS_WAVE + (int)L.ia[hi]], vs_pair_term(L.a[lo], L.a[hi], table));
+                }
+            } else {
+                const int total = ma * mb;
+                const float inv = 1.0f / (float)mb;
+                for (int q = lane; q < total; q += MVS_WAVE) {
+                    const int i = (int)(((float)q + 0.5f) * inv);    // q / mb: q < 4096, exact
+                    const int j = q - i * mb;
+                    atomicAdd(&acc[(int)L.ia[i] * MVS_WAVE + (int)L.ib[j]], vs_pair_term(L.a[i], L.b[j], table));
+                }
+            }
+            // the next point's lists overwrite these
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < MVS_WAVE * MVS_WAVE; e += VS_SCORE_THREADS) {
+        const unsigned long long t = acc[e];
+        if (t == 0) continue;
+        const int a = wi * 64 + e / MVS_WAVE, b = wj * 64 + e % MVS_WAVE;   // a < b < V: only valid bits were staged
+        const size_t at = (size_t)a * V + b;
+        atomicAdd(shared_n + at, t >> VS_COUNT_SHIFT);
+        const unsigned long long sum = t & ((1ull << VS_COUNT_SHIFT) - 1ull);
+        if (sum) atomicAdd(score_sum + at, sum);
+    }
+}
+
+__global__ __launch_bounds__(VS_THREADS) void vs_depth_hist_kernel(const float* __restrict__ xyz, int n, const float* __restrict__ proj,
+                                                                    int V, const unsigned long long* __restrict__ mask, int mask_words,
+                                                                    const int* __restrict__ prefixes, unsigned int* __restrict__ hist) {
+    for (long long i = (long long)blockIdx.x * VS_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * VS_THREADS) {
+        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        const unsigned long long* __restrict__ row = mask + (size_t)i * mask_words;
+        unsigned long long bits = 0;
+        for (int v = 0; v < V; ++v) {
+            if ((v & 63) == 0) bits = row[v >> 6];
+            if (!((bits >> (v & 63)) & 1ull)) continue;
+            const unsigned w = __float_as_uint(vs_row(proj + 12 * (size_t)v + 8, x, y, z));
+            if (!prefixes) {
+                atomicAdd(hist + (size_t)v * VS_BINS + (w >> 16), 1u);
+            } else {
+                if ((int)(w >> 16) == prefixes[2 * v]) atomicAdd(hist + ((size_t)v * 2) * VS_BINS + (w & 0xffffu), 1u);
+                if ((int)(w >> 16) == prefixes[2 * v + 1]) atomicAdd(hist + ((size_t)v * 2 + 1) * VS_BINS + (w & 0xffffu), 1u);
+            }
+        }
+    }
+}
+
+// Pass 0 with the view's histogram in LDS.  grid (blocks over the points, V): a workgroup counts one view's high halves over
+// its share of the points with LDS atomics, where thousands of points on one bin cost a cycle each instead of a trip to
+// the L2 each, and adds its non-zero bins to the view's histogram in memory.  A high half with the sign bit set (no visible
+// point has one; the mask is the caller's) goes to memory directly.
+__global__ __launch_bounds__(VS_HIST_THREADS) void vs_depth_hist_lds_kernel(const float* __restrict__ xyz, int n,
+                                                                             const float* __restrict__ proj,
+                                                                             const unsigned long long* __restrict__ mask,
+                                                                             int mask_words, unsigned int* __restrict__ hist) {
+    extern __shared__ unsigned int vs_bins[];
+    const int v = blockIdx.y;
+    for (int e = threadIdx.x; e < VS_LDS_BINS; e += VS_HIST_THREADS) vs_bins[e] = 0;
+    __syncthreads();
+    const float* __restrict__ P = proj + 12 * (size_t)v + 8;
+    unsigned int* __restrict__ out = hist + (size_t)v * VS_BINS;
+    for (long long i = (long long)blockIdx.x * VS_HIST_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * VS_HIST_THREADS) {
+        if (!((mask[(size_t)i * mask_words + (v >> 6)] >> (v & 63)) & 1ull)) continue;
+        const unsigned high = __float_as_uint(vs_row(P, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2])) >> 16;
+        if (high < (unsigned)VS_LDS_BINS) atomicAdd(&vs_bins[high], 1u);
+        else atomicAdd(out + high, 1u);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < VS_LDS_BINS; e += VS_HIST_THREADS) {
+        const unsigned c = vs_bins[e];
+        if (c) atomicAdd(out + e, c);
+    }
+}
+
+size_t vs_align(size_t b) { return (b + 255) & ~(size_t)255; }
+int vs_words(int V) { return (V + 63) / 64; }
+int vs_tiles(int V) { return vs_words(V) * (vs_words(V) + 1) / 2; }
+int vs_grid(int n) { return (int)std::min<long long>(VS_BLOCKS, mvs_cdiv(n, VS_THREADS)); }
+
+}  // namespace
+
+extern "C" int mvs_view_visibility_f32(const float* xyz, int n, const float* proj, const int* view_bits, int V, int H, int W,
+                                       float min_depth, const float* zbuf, float z_tol, unsigned long long* mask, int mask_words,
+                                       void* stream) {
+    MVS_CHECK_ARG(xyz && proj && view_bits && mask);
+    MVS_CHECK_ARG(V > 0 && H > 0 && W > 0 && mask_words > 0);
+    MVS_CHECK_ARG(min_depth >= 0.f && __builtin_isfinite(min_depth));
+    if (zbuf) MVS_CHECK_ARG(z_tol >= 1.f && __builtin_isfinite(z_tol));
+    if (n < 1 || V > VS_MAX_VIEWS || mask_words < vs_words(V)) return MVS_E_SHAPE;
+    if (H > VS_MAX_AXIS || W > VS_MAX_AXIS || (long long)V * H * W > 0x7fffffffLL) return MVS_E_SHAPE;
+    hipLaunchKernelGGL(vs_visibility_kernel, dim3(vs_grid(n)), dim3(VS_THREADS), 0, mvs_stream(stream), xyz, n, proj, view_bits, V,
+                       H, W, min_depth, zbuf, z_tol, mask, mask_words);
+    MVS_LAUNCH_RET();
+}
+
+extern "C" size_t mvs_view_scores_workspace_bytes(int n, int V) {
+    if (n < 1 || V < 1 || V > VS_MAX_VIEWS) return 0;
+    return vs_align((size_t)vs_tiles(V) * sizeof(unsigned int));
+}
+
+extern "C" int mvs_view_scores_f32(const float* xyz, int n, const int* order, const unsigned long long* mask, int mask_words,
+                                   const float* centres, int V, const unsigned short* table, long long* score_sum,
+                                   long long* shared, void* workspace, size_t workspace_bytes, void* stream) {
+    MVS_CHECK_ARG(xyz && mask && centres && table && score_sum && shared && workspace);
+    MVS_CHECK_ARG(V > 0 && mask_words > 0);
+    if (n < 1 || V > VS_MAX_VIEWS || mask_words < vs_words(V)) return MVS_E_SHAPE;
+    const int tiles = vs_tiles(V);
+    if (workspace_bytes < vs_align((size_t)tiles * sizeof(unsigned int))) return MVS_E_WORKSPACE;
+    hipStream_t st = mvs_stream(stream);
+    hipError_t e = hipMemsetAsync(score_sum, 0, (size_t)V * V * sizeof(long long), st);
+    if (e != hipSuccess) return (int)e;
+    e = hipMemsetAsync(shared, 0, (size_t)V * V * sizeof(long long), st);
+    if (e != hipSuccess) return (int)e;
+    if (V < 2) return 0;                                             // no pair
+    for (long long first = 0; first < n; first += VS_SEGMENT) {
+        const int count = (int)std::min<long long>(VS_SEGMENT, n - first);
+        e = hipMemsetAsync(workspace, 0, (size_t)tiles * sizeof(unsigned int), st);
+        if (e != hipSuccess) return (int)e;
+        const int per_tile = std::max(1, std::min(VS_SCORE_BLOCKS / tiles, mvs_cdiv(count, VS_WAVES * VS_CHUNK)));
+        hipLaunchKernelGGL(vs_score_kernel, dim3(tiles * per_tile), dim3(VS_SCORE_THREADS), 0, st, xyz, n, (int)first, count, order,
+                           mask, mask_words, centres, V, table, per_tile, static_cast<unsigned int*>(workspace),
+                           reinterpret_cast<unsigned long long*>(score_sum), reinterpret_cast<unsigned long long*>(shared));
+    }
+    MVS_LAUNCH_RET();
+}
+
+extern "C" int mvs_view_depth_hist_f32(const float* xyz, int n, const float* proj, int V, const unsigned long long* mask,
+                                       int mask_words, int pass, const int* prefixes, unsigned int* hist, void* stream) {
+    MVS_CHECK_ARG(xyz && proj && mask && hist);
+    MVS_CHECK_ARG(V > 0 && mask_words > 0 && (pass == 0 || pass == 1));
+    MVS_CHECK_ARG((pass == 1) == (prefixes != nullptr));
+    if (n < 1 || V > VS_MAX_VIEWS || mask_words < vs_words(V)) return MVS_E_SHAPE;
+    hipStream_t st = mvs_stream(stream);
+    hipError_t e = hipMemsetAsync(hist, 0, (size_t)V * (pass + 1) * VS_BINS * sizeof(unsigned int), st);
+    if (e != hipSuccess) return (int)e;
+    if (pass == 0) {
+        const size_t lds = (size_t)VS_LDS_BINS * sizeof(unsigned int);
+        e = hipFuncSetAttribute((const void*)vs_depth_hist_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        const int bx = std::max(1, std::min(mvs_cdiv(n, VS_HIST_THREADS), VS_HIST_BLOCKS / V));
+        hipLaunchKernelGGL(vs_depth_hist_lds_kernel, dim3(bx, V), dim3(VS_HIST_THREADS), lds, st, xyz, n, proj, mask, mask_words, hist);
+    } else {
+        hipLaunchKernelGGL(vs_depth_hist_kernel, dim3(vs_grid(n)), dim3(VS_THREADS), 0, st, xyz, n, proj, V, mask, mask_words,
+                           prefixes, hist);
+    }
+    MVS_LAUNCH_RET();
+}
