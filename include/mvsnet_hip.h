@@ -755,6 +755,46 @@ int mvs_view_scores_f32(const float* xyz, int n, const int* order, const unsigne
 int mvs_view_depth_hist_f32(const float* xyz, int n, const float* proj, int V, const unsigned long long* mask, int mask_words,
                             int pass, const int* prefixes, unsigned int* hist, void* stream);
 
+/* TSDF fusion of depth maps into a volume and surface-nets extraction of a triangle mesh (csrc/tsdf.hip; semantics in
+ * mvsnet_amd/mesh.py).  The volume has nx x ny x nz nodes, node (i, j, k) at linear index (k ny + j) nx + i and at
+ * origin + voxel (i, j, k); at most 2^31-1 nodes (MVS_E_SHAPE beyond).
+ *   origin        [host] 3 finite floats;  voxel > 0 and trunc > 0, finite
+ *   sum, count    (nz,ny,nx) float32 / int32: the truncated signed distances added so far and their number
+ *   rgb_sum       NULL or (nz,ny,nx,3) uint32, with rgb_count (nz,ny,nx) int32: colour sums and their number
+ * mvs_tsdf_integrate_f32 adds the V views of one size H x W, in ascending order, to sum and count (and, when images is not
+ * NULL, to rgb_sum and rgb_count, which are then required); a later call continues the same sums.
+ *   depth, prob   (V,H,W) float32; a pixel counts when depth > 0, finite and prob >= prob_threshold (not NaN)
+ *   proj          [device] V*12 floats, as mvs_render_points_f32 takes them
+ *   images        NULL or (V,img_h,img_w,3) uint8
+ *   flags         reserved, must be 0
+ *   workspace     mvs_tsdf_integrate_workspace_bytes(V, H, W) bytes (0 for invalid sizes): the filtered depth maps
+ * MVS_E_SHAPE for H, W, img_h or img_w beyond 2^24 or V*H*W beyond 2^31-1.
+ * mvs_surface_nets_count_f32 classifies cells and node edges (a node is observed when count >= min_count >= 1):
+ *   totals        [device] 2 int32, cleared by the call: the number of vertices M and of triangles F
+ *   workspace     mvs_surface_nets_workspace_bytes(nx, ny, nz) bytes: per cell, in linear cell order
+ *                 (k (ny-1) + j) (nx-1) + i, an int32 with bit 0 = valid and bit 1 = active (one zero when an axis has one
+ *                 node), then, 256-byte aligned, per node an int32 triangle count.  The caller scans both
+ * mvs_surface_nets_write_f32 writes the mesh from the same volume, min_count and workspace as the count call left them:
+ *   cell_rank     [device] per cell int32: the inclusive scan of the active bits (a cell's vertex id is its rank - 1)
+ *   face_end      [device] per node int32: the inclusive scan of the triangle counts
+ *   M, F          capacities of the outputs; a vertex or triangle beyond them is not written
+ *   vertices      (M,3) float32;  colours (M,3) uint8 (0 without rgb_sum);  faces (F,3) int32, ordered by node, then axis
+ * All three only enqueue on `stream`: nothing is allocated, nothing synchronised, a node or cell has one writer and the only
+ * atomics are the two integer totals, so the same inputs give the same bytes.  Every argument is checked before the first
+ * GPU call (MVS_E_BADARG, MVS_E_SHAPE, MVS_E_WORKSPACE) and the outputs are untouched on error. */
+size_t mvs_tsdf_integrate_workspace_bytes(int V, int H, int W);
+int mvs_tsdf_integrate_f32(const float* depth, const float* prob, int V, int H, int W, const float* proj,
+                           const unsigned char* images, int img_h, int img_w, const float* origin, float voxel, int nx, int ny,
+                           int nz, float trunc, float prob_threshold, int flags, float* sum, int* count, unsigned int* rgb_sum,
+                           int* rgb_count, void* workspace, size_t workspace_bytes, void* stream);
+size_t mvs_surface_nets_workspace_bytes(int nx, int ny, int nz);
+int mvs_surface_nets_count_f32(const float* sum, const int* count, int nx, int ny, int nz, int min_count, int* totals,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int mvs_surface_nets_write_f32(const float* sum, const int* count, const unsigned int* rgb_sum, const int* rgb_count,
+                               const float* origin, float voxel, int nx, int ny, int nz, int min_count, const int* cell_rank,
+                               const int* face_end, int M, int F, float* vertices, unsigned char* colours, int* faces,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,13 @@ SIGNATURES = {
     "mvs_view_scores_workspace_bytes": (_sz, [_i, _i]),
     "mvs_view_scores_f32": (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "mvs_view_depth_hist_f32": (_i, [_p, _i, _p, _i, _p, _i, _i, _p, _p, _p]),
+    "mvs_tsdf_integrate_workspace_bytes": (_sz, [_i] * 3),
+    "mvs_tsdf_integrate_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _i, C.POINTER(C.c_float), _f, _i, _i, _i, _f, _f, _i, _p, _p, _p,
+                                    _p, _p, _sz, _p]),
+    "mvs_surface_nets_workspace_bytes": (_sz, [_i] * 3),
+    "mvs_surface_nets_count_f32": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "mvs_surface_nets_write_f32": (_i, [_p, _p, _p, _p, C.POINTER(C.c_float), _f, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _sz,
+                                        _p]),
 }
 
 CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}

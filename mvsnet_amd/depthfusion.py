@@ -14,7 +14,7 @@ With --fusion hip, steps 2 and 3 are replaced by this project's own geometric-co
 (mvsnet_amd.fusion: a HIP kernel, not bit-compatible with fusibile), which writes
 points_mvsnet/consistencyCheck-<YYYYmmdd-HHMMSS>/final3d_model.ply, the path the reference's scripts look for:
     python -m mvsnet_amd.depthfusion --dense_folder <dir> --fusion hip [--reproj_threshold 1.0]
-        [--depth_rel_threshold 0.01] [--no_dedupe] [--fusion_sources {all,listed}]
+        [--depth_rel_threshold 0.01] [--no_dedupe] [--fusion_sources {all,listed}] [--mesh]
         [--eval_gt G.ply [--eval_max_dist 20] [--eval_thresholds 0.5,1,2]]
         [--normals] [--normal_angle_threshold DEG] [--jump_threshold 0.05] [--write_normal_maps]
 --normals estimates surface normals from the depth maps on the GPU and writes the PLY as x y z nx ny nz red green blue
@@ -138,11 +138,12 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
 
 def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent,
                dedupe=True, fusion_sources="all", eval_gt=None, eval_max_dist=20.0, eval_thresholds=(), normals=False,
-               normal_angle_threshold=None, jump_threshold=0.05, write_normal_maps=False):
+               normal_angle_threshold=None, jump_threshold=0.05, write_normal_maps=False, mesh=False):
     """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply
     (with normals: x y z nx ny nz red green blue; write_normal_maps: depths_mvsnet/<idx>_normal.pfm, camera frame).
     With eval_gt (a PLY), the fused cloud is evaluated against it on the device (mvsnet_amd.evaluate) and the metrics are
-    written to metrics.json next to the PLY."""
+    written to metrics.json next to the PLY.  With mesh, mvsnet_amd.mesh writes mesh.ply beside it: TSDF fusion and surface
+    nets of the same depth maps under the same consistency criteria."""
     import json
     import time
     from . import fusion
@@ -172,6 +173,11 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
         with open(os.path.join(out, "metrics.json"), "w") as f:
             f.write(json.dumps(metrics) + "\n")
         print("evaluated against %s: %s" % (eval_gt, json.dumps(metrics)))
+    if mesh:
+        from .mesh import mesh_dense_folder
+        print("meshed: %s" % json.dumps(mesh_dense_folder(
+            dense_folder, os.path.join(out, "mesh.ply"), fusion_sources=fusion_sources, prob_threshold=prob_threshold,
+            reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent)))
     return path
 
 
@@ -213,9 +219,11 @@ def main(argv=None):
                     help="--fusion hip: relative depth jump beyond which a neighbour is not used for a normal (0.05)")
     ap.add_argument("--write_normal_maps", action="store_true",
                     help="--fusion hip: write depths_mvsnet/<idx>_normal.pfm (colour PFM, camera frame)")
+    ap.add_argument("--mesh", action="store_true",
+                    help="--fusion hip: also write mesh.ply beside final3d_model.ply (mvsnet_amd.mesh, default options)")
     a = ap.parse_args(argv)
     if a.fusion != "hip":
-        for flag, given in (("--normals", a.normals), ("--normal_angle_threshold", a.normal_angle_threshold is not None),
+        for flag, given in (("--mesh", a.mesh), ("--normals", a.normals), ("--normal_angle_threshold", a.normal_angle_threshold is not None),
                             ("--jump_threshold", a.jump_threshold is not None), ("--write_normal_maps", a.write_normal_maps)):
             if given:
                 raise SystemExit("%s needs --fusion hip" % flag)
@@ -250,7 +258,7 @@ def main(argv=None):
                           eval_max_dist=a.eval_max_dist, eval_thresholds=eval_thresholds, normals=a.normals,
                           normal_angle_threshold=a.normal_angle_threshold,
                           jump_threshold=0.05 if a.jump_threshold is None else a.jump_threshold,
-                          write_normal_maps=a.write_normal_maps)
+                          write_normal_maps=a.write_normal_maps, mesh=a.mesh)
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")

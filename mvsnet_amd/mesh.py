@@ -1,0 +1,453 @@
+"""From depth maps to a surface on the MI355X: TSDF fusion of a session's depth maps into a volume and extraction of a triangle
+mesh by naive surface nets, the last stage between the depth maps and a model that can be published.
+
+    python -m mvsnet_amd.mesh --dense_folder DIR [--out mesh.ply] [--voxel S | --resolution R] [--bounds x0:y0:z0:x1:y1:z1]
+        [--trunc_voxels 4] [--prob_threshold 0.8] [--num_consistent 3] [--min_count 1] [--fusion_sources all|listed] [--force]
+
+The kernels are csrc/tsdf.hip (mvs_tsdf_integrate_f32, mvs_surface_nets_count_f32, mvs_surface_nets_write_f32); torch owns the
+device memory and the two scans between counting and writing.
+
+Semantics (shared by the kernels, tests/mesh_reference.py and the tests).  Conventions are fusion.py's and render.py's: cam
+(2,4,4) with E = cam[0] world -> camera and K = cam[1][:3,:3]; pixel (x, y) is column x, row y at integer coordinates; views
+of one call share one size H x W; P_v = K_v [R_v | t_v] is composed in float64 and rounded to float32 once
+(``render.projection_tables``).  All device arithmetic is float32 with every product, sum and quotient rounded on its own (no
+fused multiply-add, correctly rounded divisions), so float32 numpy and the kernels agree byte for byte.
+  * Volume: nx x ny x nz nodes, node (i, j, k) at linear index (k ny + j) nx + i, at most 2^31 - 1 of them.  Its position
+    per axis is o + s float(i): a rounded product, then a rounded sum.  Per node the volume holds sum (float32), count
+    (int32) and, with colour, rgb_sum (3 x uint32) and rgb_count (int32).
+  * Integration: the views of one call in ascending order; a later call continues the same sums.  For node p and view v:
+    (u, v, w) are the three rows r = ((P0 X + P1 Y) + P2 Z) + P3 of render.py.  The node is a candidate when w is finite and
+    w > 0; fx = floor(u / w + 0.5) and fy likewise must be finite and inside [0, W - 1] x [0, H - 1], compared in float;
+    d = df[v, fy, fx] must be > 0, where df is the filtered depth: D where D > 0, finite and prob >= prob_threshold, else 0.
+    sdf = d - w; the observation is dropped when sdf < -trunc.  Otherwise t = min(sdf / trunc, 1), sum += t, count += 1.
+    Colour, when images are given and sdf <= trunc: the nearest image pixel is ((2 fx + 1) W_img) // (2 W), likewise in y
+    (fusion.py's rule, in integers); its three bytes are added to rgb_sum and rgb_count += 1.
+  * A node is observed when count >= min_count (default 1); its value is f = sum / float(count); it is inside when it is
+    observed and f < 0 (so f == 0 is outside).
+  * Surface nets.  Cell (i, j, k), 0 <= i < nx - 1 and so on, has linear index (k (ny - 1) + j) (nx - 1) + i and the corners
+    (i + dx, j + dy, k + dz).  A cell is valid when all 8 corners are observed, active when it is valid and its corners are
+    neither all inside nor all outside.  Each active cell has one vertex; its id is the cell's rank among the active cells
+    in ascending linear index.
+  * Vertex position: for axis a = 0, 1, 2 with b = (a + 1) mod 3, c = (a + 2) mod 3, the four cell edges along a in the order
+    (off_c, off_b) = (0,0), (0,1), (1,0), (1,1).  An edge from its lower corner A to its upper corner B crosses when
+    inside(A) != inside(B); it then has tau = f_A / (f_A - f_B) and adds the local point (tau on a, off_b on b, off_c on c)
+    to a float32 accumulator, in that order, and 1 to m.  local = acc / float(m); the coordinate on each axis is
+    o + s (float(i) + local).
+  * Vertex colour: R = sum of rgb_sum and n = sum of rgb_count over the 8 corners; the byte is (2 R + n) // (2 n), 0 when
+    n = 0 (and without colour).
+  * Faces: a node edge along axis a from q to q + e_a with both ends observed and inside(q) != inside(q + e_a) has the four
+    cells c0 = q - e_b - e_c, c1 = q - e_c, c2 = q, c3 = q - e_b.  When all four exist and are valid, the edge gives the
+    triangles (c0, c1, c2), (c0, c2, c3) if inside(q), else (c0, c2, c1), (c0, c3, c2): normals point from inside to
+    outside, towards the cameras.  Faces are ordered by the node index of q ascending, then axis, then the two triangles.
+  * Outputs: vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32.
+
+The mesh of a session (``mesh_depth_maps``, the command line): the depth maps are first masked to the pixels the project's
+geometric-consistency fusion keeps (``consistency_masks``: fusion.py's criteria without dedupe), which removes the outliers
+the probability filter lets through; num_consistent = 0 leaves the probability filter alone.  Default bounds are the box of
+the fusion's kept points, widened by trunc plus one voxel.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+MAX_NODES = 2 ** 31 - 1
+
+MESH_PLY_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                   "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\n"
+                   "property list uchar int vertex_indices\nend_header\n")
+_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+# ------------------------------------------------------------------------------------------------ host side, no GPU needed
+
+def check_volume(origin, voxel, dims, trunc):
+    """-> (origin (3,) float32, voxel, dims (nx, ny, nz), trunc) as the kernels take them; ValueError otherwise."""
+    o = np.asarray(origin, np.float64).reshape(-1)
+    with np.errstate(over="ignore"):
+        o32 = o.astype(np.float32)
+    if o.shape != (3,) or not np.isfinite(o32).all():
+        raise ValueError("origin must be three finite numbers, got %r" % (origin,))
+    v32, t32 = float(np.float32(voxel)), float(np.float32(trunc))
+    if not (v32 > 0 and math.isfinite(v32)):
+        raise ValueError("voxel must be positive and finite, got %r" % (voxel,))
+    if not (t32 > 0 and math.isfinite(t32)):
+        raise ValueError("trunc must be positive and finite, got %r" % (trunc,))
+    try:
+        d = tuple(dims)
+        if len(d) != 3 or any(isinstance(n, bool) or int(n) != n or int(n) < 1 for n in d):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("dims must be three positive integers (nx, ny, nz), got %r" % (dims,))
+    d = tuple(int(n) for n in d)
+    if d[0] * d[1] * d[2] > MAX_NODES:
+        raise ValueError("a volume of %d x %d x %d nodes is beyond the kernels' int32 indices" % d)
+    return o32, v32, d, t32
+
+
+def check_min_count(min_count):
+    if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 1:
+        raise ValueError("min_count must be a positive integer, got %r" % (min_count,))
+    return int(min_count)
+
+
+def choose_volume(lo, hi, voxel=None, resolution=256, margin=0.0, margin_voxels=0.0):
+    """A volume around the box [lo, hi] widened on every side by margin + margin_voxels * voxel, in float64
+    -> (origin (3,), voxel, dims (nx, ny, nz)).  With a voxel, dims follow; without one, the voxel is chosen so that the
+    longest axis has `resolution` nodes.  Every axis gets at least two nodes."""
+    lo, hi = np.asarray(lo, np.float64).reshape(-1), np.asarray(hi, np.float64).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (hi < lo).any():
+        raise ValueError("bounds must be finite with lo <= hi, got %r and %r" % (lo, hi))
+    margin, margin_voxels = float(margin), float(margin_voxels)
+    if not (margin >= 0 and margin_voxels >= 0 and math.isfinite(margin) and math.isfinite(margin_voxels)):
+        raise ValueError("margins must be >= 0 and finite")
+    extent = float((hi - lo).max()) + 2 * margin
+    if voxel is None:
+        if isinstance(resolution, bool) or int(resolution) != resolution or int(resolution) < 2:
+            raise ValueError("resolution must be an integer >= 2, got %r" % (resolution,))
+        steps = int(resolution) - 1 - 2 * margin_voxels
+        if not (steps > 0 and extent > 0):
+            raise ValueError("no voxel fits: resolution %r, margin of %r voxels, extent %r" % (resolution, margin_voxels, extent))
+        voxel = extent / steps
+    voxel = float(voxel)
+    if not (voxel > 0 and math.isfinite(voxel)):
+        raise ValueError("voxel must be positive and finite, got %r" % (voxel,))
+    pad = margin + margin_voxels * voxel
+    origin = lo - pad
+    dims = tuple(int(max(2, math.ceil(float(e) / voxel - 1e-9) + 1)) for e in (hi + pad - origin))
+    if dims[0] * dims[1] * dims[2] > MAX_NODES:
+        raise ValueError("a volume of %d x %d x %d nodes is beyond the kernels' int32 indices" % dims)
+    return origin, voxel, dims
+
+
+def write_mesh_ply(path, vertices, colours, faces):
+    """Binary little-endian PLY: vertex x y z float, red green blue uchar; face list uchar int vertex_indices."""
+    vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
+    colours = np.asarray(colours, np.uint8).reshape(-1, 3)
+    faces = np.asarray(faces, np.int32).reshape(-1, 3)
+    if len(vertices) != len(colours):
+        raise ValueError("vertices and colours differ in length")
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(vertices)):
+        raise ValueError("faces name a vertex outside 0..%d" % (len(vertices) - 1))
+    v = np.empty(len(vertices), _VERTEX_DTYPE)
+    v["x"], v["y"], v["z"] = vertices[:, 0], vertices[:, 1], vertices[:, 2]
+    v["red"], v["green"], v["blue"] = colours[:, 0], colours[:, 1], colours[:, 2]
+    f = np.empty(len(faces), _FACE_DTYPE)
+    f["n"], f["v"] = 3, faces
+    with open(path, "wb") as out:
+        out.write((MESH_PLY_HEADER % (len(v), len(f))).encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+
+
+def read_mesh_ply(path):
+    """Reads what write_mesh_ply writes -> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32)."""
+    data = open(path, "rb").read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii")
+    try:
+        m = int(head.split("element vertex ")[1].split("\n")[0])
+        nf = int(head.split("element face ")[1].split("\n")[0])
+    except (IndexError, ValueError):
+        raise ValueError("%s: not a PLY written by write_mesh_ply" % path)
+    if head != MESH_PLY_HEADER % (m, nf) or len(data) != end + m * _VERTEX_DTYPE.itemsize + nf * _FACE_DTYPE.itemsize:
+        raise ValueError("%s: not a PLY written by write_mesh_ply" % path)
+    v = np.frombuffer(data, _VERTEX_DTYPE, count=m, offset=end)
+    f = np.frombuffer(data, _FACE_DTYPE, count=nf, offset=end + m * _VERTEX_DTYPE.itemsize)
+    if nf and (f["n"] != 3).any():
+        raise ValueError("%s: a face is not a triangle" % path)
+    return (np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float32), np.stack([v["red"], v["green"], v["blue"]], 1).astype(np.uint8),
+            np.ascontiguousarray(f["v"]).astype(np.int32).reshape(-1, 3))
+
+
+def parse_bounds(text):
+    """"x0:y0:z0:x1:y1:z1" -> (lo (3,), hi (3,)) float64."""
+    tok = str(text).split(":")
+    try:
+        if len(tok) != 6:
+            raise ValueError
+        b = np.array([float(t) for t in tok])
+    except ValueError:
+        raise ValueError("bounds %r: x0:y0:z0:x1:y1:z1 expected" % (text,))
+    if not np.isfinite(b).all() or (b[3:] <= b[:3]).any():
+        raise ValueError("bounds %r: finite numbers with x0 < x1, y0 < y1, z0 < z1 expected" % (text,))
+    return b[:3], b[3:]
+
+
+def _check_views(depths, probs, cams, images):
+    """The shapes of one integrate call -> (V, H, W); ValueError otherwise.  Works on numpy arrays and tensors alike."""
+    ds, ps = tuple(depths.shape), tuple(probs.shape)
+    if len(ds) != 3 or ps != ds or 0 in ds:
+        raise ValueError("depths and probs must be (V,H,W) of one size, got %s and %s" % (ds, ps))
+    if tuple(cams.shape) != (ds[0], 2, 4, 4):
+        raise ValueError("cams must be (%d,2,4,4), got %s" % (ds[0], tuple(cams.shape)))
+    if images is not None:
+        s = tuple(images.shape)
+        if len(s) != 4 or s[0] != ds[0] or s[3] != 3 or 0 in s:
+            raise ValueError("images must be (%d,H,W,3) uint8, got %s" % (ds[0], s))
+    return ds
+
+
+# ------------------------------------------------------------------------------------------------ device side
+
+def _device(device):
+    import torch
+    from . import _lib
+    dev = torch.device(device) if device is not None else torch.device("cuda")
+    if dev.type != "cuda":
+        raise ValueError("TSDF fusion runs on a GPU device, got %s" % dev)
+    if not torch.cuda.is_available():
+        raise _lib.MvsnetHipError("TSDF fusion runs on the GPU (HIP); no GPU is visible to this process")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+class TsdfVolume:
+    """A volume on the device.  ``integrate`` may be called repeatedly (a session can be fed in groups of views) and only
+    enqueues on torch's current stream; ``extract`` synchronises once, to size its outputs."""
+
+    def __init__(self, origin, voxel, dims, trunc, colour=False, device=None):
+        import torch
+        self.origin, self.voxel, self.dims, self.trunc = check_volume(origin, voxel, dims, trunc)      # before any GPU work
+        self.colour = bool(colour)
+        self.dev = _device(device)
+        nx, ny, nz = self.dims
+        self._origin_c = (ctypes.c_float * 3)(*[float(v) for v in self.origin])
+        with torch.cuda.device(self.dev):
+            self.sum = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.dev)
+            self.count = torch.zeros((nz, ny, nx), dtype=torch.int32, device=self.dev)
+            self.rgb_sum = self.rgb_count = None
+            if self.colour:
+                # torch has no uint32 arithmetic to speak of: the kernel's uint32 sums live in an int32 tensor
+                self.rgb_sum = torch.zeros((nz, ny, nx, 3), dtype=torch.int32, device=self.dev)
+                self.rgb_count = torch.zeros((nz, ny, nx), dtype=torch.int32, device=self.dev)
+        self._workspace = None
+
+    def _views(self, x, name, dtype):
+        import torch
+        if isinstance(x, torch.Tensor):
+            if x.dtype != dtype:
+                raise ValueError("%s must be %s, got %s" % (name, dtype, x.dtype))
+            return x.to(self.dev).contiguous()
+        return torch.as_tensor(x).to(self.dev)
+
+    def integrate(self, depths, probs, cams, images=None, prob_threshold=0.8):
+        """Adds V views, in ascending order, to the volume.  depths, probs: (V,H,W) float32 arrays, tensors or lists of
+        (H,W); cams (V,2,4,4); images None or (V,Hi,Wi,3) uint8, used only by a volume made with colour."""
+        import torch
+        from . import _lib
+        from .fusion import FusionPlan
+        from .render import projection_tables
+        pt = float(prob_threshold)
+        if math.isnan(pt):
+            raise ValueError("prob_threshold must not be NaN")
+        depths, probs = FusionPlan._host(depths, "depth maps", np.float32), FusionPlan._host(probs, "probability maps", np.float32)
+        images = None if images is None or not self.colour else FusionPlan._host(images, "images", np.uint8)
+        cams = np.asarray(cams.cpu().numpy() if hasattr(cams, "cpu") else cams, np.float64)
+        V, H, W = _check_views(depths, probs, cams, images)
+        lib = _lib.load()
+        nx, ny, nz = self.dims
+        with torch.cuda.device(self.dev):
+            d, p = self._views(depths, "depth maps", torch.float32), self._views(probs, "probability maps", torch.float32)
+            im = None if images is None else self._views(images, "images", torch.uint8)
+            proj = torch.as_tensor(projection_tables(cams)).to(self.dev)
+            wsb = lib.mvs_tsdf_integrate_workspace_bytes(V, H, W)
+            if wsb == 0:
+                raise ValueError("integrate: %d views of %d x %d are beyond the kernel's index range" % (V, H, W))
+            if self._workspace is None or self._workspace.numel() < wsb:
+                self._workspace = torch.empty(wsb, dtype=torch.uint8, device=self.dev)
+            rc = lib.mvs_tsdf_integrate_f32(
+                _lib.ptr(d), _lib.ptr(p), V, H, W, _lib.ptr(proj), _lib.ptr(im), im.shape[1] if im is not None else 0,
+                im.shape[2] if im is not None else 0, self._origin_c, self.voxel, nx, ny, nz, self.trunc, pt, 0,
+                _lib.ptr(self.sum), _lib.ptr(self.count), _lib.ptr(self.rgb_sum) if im is not None else None,
+                _lib.ptr(self.rgb_count) if im is not None else None, _lib.ptr(self._workspace), self._workspace.numel(),
+                _lib.stream_ptr())
+            _lib.check(rc, "mvs_tsdf_integrate_f32")
+        return self
+
+    def extract(self, min_count=1):
+        """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation."""
+        import torch
+        from . import _lib
+        min_count = check_min_count(min_count)
+        lib = _lib.load()
+        nx, ny, nz = self.dims
+        nodes = nx * ny * nz
+        cells = max(nx - 1, 0) * max(ny - 1, 0) * max(nz - 1, 0)
+        with torch.cuda.device(self.dev):
+            wsb = lib.mvs_surface_nets_workspace_bytes(nx, ny, nz)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=self.dev)
+            totals = torch.empty(2, dtype=torch.int32, device=self.dev)
+            rc = lib.mvs_surface_nets_count_f32(_lib.ptr(self.sum), _lib.ptr(self.count), nx, ny, nz, min_count, _lib.ptr(totals),
+                                                _lib.ptr(ws), wsb, _lib.stream_ptr())
+            _lib.check(rc, "mvs_surface_nets_count_f32")
+            words = ws.view(torch.int32)
+            face_at = ((max(cells, 1) * 4 + 255) // 256 * 256) // 4
+            cell_rank = torch.cumsum(words[:max(cells, 1)] >> 1, 0, dtype=torch.int32)
+            face_end = torch.cumsum(words[face_at:face_at + nodes], 0, dtype=torch.int32)
+            M, F = (int(v) for v in totals.cpu().numpy())                       # the one synchronisation
+            if M < 0 or F < 0:
+                raise ValueError("the mesh is beyond int32 indices")
+            vertices = torch.empty((M, 3), dtype=torch.float32, device=self.dev)
+            colours = torch.empty((M, 3), dtype=torch.uint8, device=self.dev)
+            faces = torch.empty((F, 3), dtype=torch.int32, device=self.dev)
+            if M:
+                rc = lib.mvs_surface_nets_write_f32(
+                    _lib.ptr(self.sum), _lib.ptr(self.count), _lib.ptr(self.rgb_sum), _lib.ptr(self.rgb_count), self._origin_c,
+                    self.voxel, nx, ny, nz, min_count, _lib.ptr(cell_rank), _lib.ptr(face_end), M, F, _lib.ptr(vertices),
+                    _lib.ptr(colours), _lib.ptr(faces) if F else None, _lib.ptr(ws), wsb, _lib.stream_ptr())
+                _lib.check(rc, "mvs_surface_nets_write_f32")
+            return vertices.cpu().numpy(), colours.cpu().numpy(), faces.cpu().numpy()
+
+    def tsdf(self):
+        """For inspection -> (f (nz,ny,nx) float32 = sum / count, NaN where count is 0, count (nz,ny,nx) int32) as numpy."""
+        s, c = self.sum.cpu().numpy(), self.count.cpu().numpy()
+        with np.errstate(all="ignore"):
+            return np.where(c > 0, s / c.astype(np.float32), np.float32(np.nan)), c
+
+    def state(self):
+        """The raw sums as numpy: dict(sum, count, rgb_sum (uint32) or None, rgb_count or None)."""
+        return dict(sum=self.sum.cpu().numpy(), count=self.count.cpu().numpy(),
+                    rgb_sum=None if self.rgb_sum is None else self.rgb_sum.cpu().numpy().view(np.uint32),
+                    rgb_count=None if self.rgb_count is None else self.rgb_count.cpu().numpy())
+
+
+def _consistency(depths, probs, cams, *, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, num_consistent=3,
+                 sources=None, device=None):
+    from .fusion import FusionPlan
+    plan = FusionPlan(depths, probs, cams, None, prob_threshold=prob_threshold, reproj_threshold=reproj_threshold,
+                      depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent, sources=sources, dedupe=False,
+                      device=device)
+    plan.enqueue()
+    xyz, _, view, pixel = plan.result(with_pixels=True)
+    masks = np.zeros((plan.V, plan.H * plan.W), bool)
+    masks[view, pixel] = True
+    return masks.reshape(plan.V, plan.H, plan.W), xyz
+
+
+def consistency_masks(depths, probs, cams, **options):
+    """(V,H,W) bool: the pixels the project's geometric-consistency fusion keeps, every view on its own (dedupe off).
+    Options: prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent, sources, device (fusion.FusionPlan's)."""
+    return _consistency(depths, probs, cams, **options)[0]
+
+
+def mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution=None, bounds=None, trunc_voxels=4,
+                    num_consistent=3, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, sources=None,
+                    min_count=1, device=None):
+    """V depth maps -> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32).  Give a voxel or a resolution (nodes
+    along the longest axis, 256 when neither is given); bounds (lo, hi) default to the box of the consistent points."""
+    from .fusion import FusionPlan
+    if voxel is not None and resolution is not None:
+        raise ValueError("give a voxel or a resolution, not both")
+    tv = float(trunc_voxels)
+    if not (tv > 0 and math.isfinite(tv)):
+        raise ValueError("trunc_voxels must be positive and finite, got %r" % (trunc_voxels,))
+    min_count = check_min_count(min_count)
+    if voxel is None and resolution is None:
+        resolution = 256
+    depths, probs = FusionPlan._host(depths, "depth maps", np.float32), FusionPlan._host(probs, "probability maps", np.float32)
+    to_numpy = lambda x: x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+    depths, probs = to_numpy(depths), to_numpy(probs)
+    xyz = None
+    if num_consistent > 0 or bounds is None:
+        masks, xyz = _consistency(depths, probs, cams, prob_threshold=prob_threshold, reproj_threshold=reproj_threshold,
+                                  depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent, sources=sources,
+                                  device=device)
+        if num_consistent > 0:
+            depths = np.where(masks, depths, np.float32(0))
+    if bounds is None:
+        if len(xyz) == 0:
+            raise ValueError("no pixel is consistent in %g views: nothing to bound the volume with" % num_consistent)
+        lo, hi = xyz.min(0).astype(np.float64), xyz.max(0).astype(np.float64)
+        origin, voxel, dims = choose_volume(lo, hi, voxel, resolution, margin_voxels=tv + 1)
+    else:
+        origin, voxel, dims = choose_volume(bounds[0], bounds[1], voxel, resolution)
+    vol = TsdfVolume(origin, voxel, dims, tv * voxel, colour=images is not None, device=device)
+    vol.integrate(depths, probs, cams, images, prob_threshold=prob_threshold)
+    return vol.extract(min_count)
+
+
+# ------------------------------------------------------------------------------------------------ command line
+
+def build_parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dense_folder", required=True, help="dense folder: depths_mvsnet/<idx>_init.pfm, _prob.pfm, .txt[, .jpg]")
+    ap.add_argument("--out", default=None, help="output PLY (default <dense_folder>/points_mvsnet/mesh.ply)")
+    size = ap.add_mutually_exclusive_group()
+    size.add_argument("--voxel", type=float, default=None, help="node spacing in world units")
+    size.add_argument("--resolution", type=int, default=None, help="nodes along the longest axis (256 when no --voxel is given)")
+    ap.add_argument("--bounds", default=None, help="x0:y0:z0:x1:y1:z1 (default: the box of the consistent points, widened)")
+    ap.add_argument("--trunc_voxels", type=float, default=4.0, help="truncation distance in voxels")
+    ap.add_argument("--prob_threshold", type=float, default=0.8)
+    ap.add_argument("--num_consistent", type=float, default=3, help="views that must agree on a pixel (0: probability filter alone)")
+    ap.add_argument("--min_count", type=int, default=1, help="observations a node needs")
+    ap.add_argument("--fusion_sources", choices=("all", "listed"), default="all",
+                    help="consistency against every other view, or the neighbours of pair.txt / covisibility.json")
+    ap.add_argument("--force", action="store_true", help="overwrite an existing output file")
+    return ap
+
+
+def parse_args(argv=None):
+    """-> the namespace with .bounds parsed and the options checked (SystemExit otherwise)."""
+    a = build_parser().parse_args(argv)
+    try:
+        a.bounds = parse_bounds(a.bounds) if a.bounds is not None else None
+        a.min_count = check_min_count(a.min_count)
+        if not (a.trunc_voxels > 0 and math.isfinite(a.trunc_voxels)):
+            raise ValueError("--trunc_voxels must be positive and finite, got %r" % (a.trunc_voxels,))
+        if a.voxel is not None and not (a.voxel > 0 and math.isfinite(a.voxel)):
+            raise ValueError("--voxel must be positive and finite, got %r" % (a.voxel,))
+        if a.resolution is not None and a.resolution < 2:
+            raise ValueError("--resolution must be at least 2, got %r" % (a.resolution,))
+        if math.isnan(a.prob_threshold) or not a.num_consistent >= 0:
+            raise ValueError("--prob_threshold must be a number and --num_consistent >= 0")
+    except ValueError as e:
+        raise SystemExit("mvsnet_amd.mesh: %s" % e)
+    if a.out is None:
+        a.out = os.path.join(a.dense_folder, "points_mvsnet", "mesh.ply")
+    return a
+
+
+def prepare_output(a):
+    """An existing output is refused without --force, before any GPU work."""
+    if os.path.exists(a.out) and not a.force:
+        raise SystemExit("mvsnet_amd.mesh: %s exists; pass --force to overwrite it" % a.out)
+    return a.out
+
+
+def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", **options):
+    """The dense folder's depth maps -> the PLY at `out`; returns the report the command line prints."""
+    from . import fusion
+    indices, depths, probs, cams, images = fusion.load_dense_folder(dense_folder)
+    sources = fusion.listed_sources(dense_folder, indices) if fusion_sources == "listed" else None
+    vertices, colours, faces = mesh_depth_maps(depths, probs, cams, images, sources=sources, **options)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    write_mesh_ply(out, vertices, colours, faces)
+    return {"views": len(indices), "vertices": int(len(vertices)), "faces": int(len(faces)), "out": out}
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    out = prepare_output(a)
+    from .depthfusion import _gpu_ready
+    why = _gpu_ready()
+    if why is not None:
+        raise SystemExit("mvsnet_amd.mesh needs a GPU and the HIP library: %s" % why)
+    try:
+        report = mesh_dense_folder(a.dense_folder, out, fusion_sources=a.fusion_sources, voxel=a.voxel, resolution=a.resolution,
+                                   bounds=a.bounds, trunc_voxels=a.trunc_voxels, num_consistent=a.num_consistent,
+                                   prob_threshold=a.prob_threshold, min_count=a.min_count)
+    except (ValueError, OSError) as e:
+        raise SystemExit("mvsnet_amd.mesh: %s" % e)
+    print(json.dumps(report))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
