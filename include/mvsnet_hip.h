@@ -795,6 +795,36 @@ int mvs_surface_nets_write_f32(const float* sum, const int* count, const unsigne
                                const int* face_end, int M, int F, float* vertices, unsigned char* colours, int* faces,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Rasterisation of a triangle mesh into per-view depth maps with a z-buffer, and interpolation of vertex attributes over
+ * the result (csrc/raster.hip; semantics in mvsnet_amd/render_mesh.py).
+ *   vertices      (M,3) float32, read only; non-finite coordinates are allowed (their faces are dropped)
+ *   faces         (F,3) int32; a face that names a vertex outside 0..M-1 is dropped and never dereferenced
+ *   order         NULL or (F) int32, a permutation of the faces: the order in which lanes take them; NULL = input order
+ *   proj          [device] 12 floats per view, as mvs_render_points_f32 takes them
+ *   min_depth     >= 0 and finite: a vertex at or below it makes its faces drop out of that view (nothing is clipped)
+ *   cull          0 keeps every face, +1 drops those of positive screen area (the back faces of an outward-wound mesh),
+ *                 -1 those of negative
+ *   large_pixels  a (face, view) pair whose clipped bounding box holds more pixels goes through the queue to the second
+ *                 kernel, where a workgroup strides over the box; queue_capacity entries of 8 bytes, and a pair that finds
+ *                 the queue full is drawn by its lane.  Neither changes a byte of the output
+ *   depth         (V,H,W) float32: per pixel the smallest perspective-correct depth of the faces that cover it, 0 where empty
+ *   index         NULL or (V,H,W) int32: that face (exact ties of depth: the smallest index), -1 where empty
+ *   workspace     mvs_raster_workspace_bytes(V, H, W, queue_capacity) bytes (0 for invalid sizes): the queue counter, the
+ *                 8-byte keys bits(z) << 32 | face of all pixels and the queue; the call clears what it needs
+ * mvs_raster_interpolate_f32: index (V,H,W) int32 as the mesh call wrote it, attr (M,C) float32 with 1 <= C <= 8 ->
+ * out (V,H,W,C) float32, perspective-correct in float64; 0 where the pixel is empty, its index is outside 0..F-1 or its face
+ * is dropped in that view.
+ * Both only enqueue on `stream`: nothing is allocated, nothing synchronised.  The only atomics on the output are 64-bit
+ * unsigned minima, so the same inputs give the same bytes in any order and grid.  Every argument is checked before the
+ * first GPU call: MVS_E_BADARG for a null pointer or an option outside the ranges above, MVS_E_SHAPE when V*H*W exceeds
+ * 2^31-1 or H or W exceeds 2^20 (256 x stays inside the guard band of 2^28), MVS_E_WORKSPACE; outputs are untouched on error. */
+size_t mvs_raster_workspace_bytes(int V, int H, int W, int queue_capacity);
+int mvs_raster_mesh_f32(const float* vertices, int M, const int* faces, int F, const int* order, const float* proj, int V,
+                        int H, int W, float min_depth, int cull, int large_pixels, int queue_capacity, float* depth,
+                        int* index, void* workspace, size_t workspace_bytes, void* stream);
+int mvs_raster_interpolate_f32(const float* vertices, int M, const int* faces, int F, const float* proj, int V, int H, int W,
+                               float min_depth, const int* index, const float* attr, int C, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,9 @@ SIGNATURES = {
     "mvs_surface_nets_count_f32": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "mvs_surface_nets_write_f32": (_i, [_p, _p, _p, _p, C.POINTER(C.c_float), _f, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _sz,
                                         _p]),
+    "mvs_raster_workspace_bytes": (_sz, [_i] * 4),
+    "mvs_raster_mesh_f32": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "mvs_raster_interpolate_f32": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _p, _i, _p, _p]),
 }
 
 CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}
