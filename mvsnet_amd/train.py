@@ -197,6 +197,7 @@ class Trainer:
         self.slots = [torch.ones(n, device=self.device) if (ones and i == 0) else torch.zeros(n, device=self.device)
                       for i in range(len(OPTIMIZER_SLOTS[optimizer]))]
         self.global_step = 0
+        self._runs = None
         self.world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
 
     # -- one optimisation step ------------------------------------------------------------------------
@@ -284,35 +285,54 @@ class Trainer:
                 torch.distributed.all_reduce(g)
         return 1.0 / self.world
 
+    def frozen(self, group):
+        """refine_only (train.py:312-315): the main network's variables are created with trainable=False, so compute_gradients
+        never sees them and the optimiser neither updates them nor touches their slots."""
+        return self.refinement and self.refine_cfg[3] == "refine_only" and group != "refine"
+
+    def trainable_runs(self):
+        """[(offset, length)] of the maximal contiguous runs of trainable variables in the flat buffer: all of it as one run
+        unless some variables are frozen."""
+        if self._runs is None:
+            runs = []
+            for (group, _l, _f), _v, o, shape in self.params.index:
+                if self.frozen(group):
+                    continue
+                n = int(np.prod(shape))
+                if runs and runs[-1][0] + runs[-1][1] == o:
+                    runs[-1] = (runs[-1][0], runs[-1][1] + n)
+                else:
+                    runs.append((o, n))
+            self._runs = runs
+        return self._runs
+
     def apply_gradients(self):
-        """average over ranks + optimiser update (train.py:444), one launch each."""
+        """average over ranks + optimiser update (train.py:444): one all-reduce, one launch per run of trainable variables
+        (one in all unless refine_only freezes the main network: a frozen variable's slots stay as they are -- an update with a
+        zero gradient would still decay RMSProp's `rms` slot)."""
         lib = _lib.load()
-        p, g = self.params.data, self.params.grad
         scale = self.reduce_gradients()
-        lr, n = self.learning_rate(), self.params.numel
+        lr = self.learning_rate()
         P = _lib.ptr
-        if self.optimizer == "rmsprop":
-            rc = lib.mvs_rmsprop_step_f32(P(p), P(g), P(self.slots[0]), P(self.slots[1]), n, lr, 0.9, 0.0, 1e-10, scale,
-                                          _lib.stream_ptr())
-        elif self.optimizer == "momentum":
-            rc = lib.mvs_momentum_step_f32(P(p), P(g), P(self.slots[0]), n, lr, 0.9, scale, _lib.stream_ptr())
-        else:
-            t = self.global_step + 1
-            lr_t = lr * math.sqrt(1.0 - 0.999 ** t) / (1.0 - 0.9 ** t)
-            rc = lib.mvs_adam_step_f32(P(p), P(g), P(self.slots[0]), P(self.slots[1]), n, lr_t, 0.9, 0.999, 1e-8, scale,
-                                       _lib.stream_ptr())
-        _lib.check(rc, "optimizer step")
-        g.zero_()
+        for o, n in self.trainable_runs():
+            p, g = self.params.data[o:o + n], self.params.grad[o:o + n]
+            s = [slot[o:o + n] for slot in self.slots]
+            if self.optimizer == "rmsprop":
+                rc = lib.mvs_rmsprop_step_f32(P(p), P(g), P(s[0]), P(s[1]), n, lr, 0.9, 0.0, 1e-10, scale, _lib.stream_ptr())
+            elif self.optimizer == "momentum":
+                rc = lib.mvs_momentum_step_f32(P(p), P(g), P(s[0]), n, lr, 0.9, scale, _lib.stream_ptr())
+            else:
+                t = self.global_step + 1
+                lr_t = lr * math.sqrt(1.0 - 0.999 ** t) / (1.0 - 0.9 ** t)
+                rc = lib.mvs_adam_step_f32(P(p), P(g), P(s[0]), P(s[1]), n, lr_t, 0.9, 0.999, 1e-8, scale, _lib.stream_ptr())
+            _lib.check(rc, "optimizer step")
+        self.params.grad.zero_()
         self.global_step += 1
 
     def train_step(self, images, cams, depth_image, depth_num, full_depth=None):
         loss, l1, l3, _ = self.loss(images, cams, depth_image, depth_num, full_depth)
         loss.backward()
-        if self.refinement and self.refine_cfg[3] == "refine_only":     # the main network's variables are not trainable
-            for (group, _l, _f), _v, o, shape in self.params.index:
-                if group != "refine":
-                    self.params.grad[o:o + int(np.prod(shape))].zero_()
-        self.apply_gradients()
+        self.apply_gradients()                                          # skips frozen variables (refine_only); zeroes all gradients
         return loss.detach(), l1.detach(), l3.detach()
 
     @torch.no_grad()

@@ -2,7 +2,9 @@
 mvsnet/model.py:257-372 (`inference`: eager variance :315-334, RegNetUS0 mvsnetworks.py:122-158 with
 batch-statistics BatchNorm network.py:492-509, soft-argmin model.py:343-366) written with differentiable
 torch-CPU float64 ops, so that torch autograd plays the role TensorFlow's autodiff has in the reference
-(train.py:428-429).  TEST INFRASTRUCTURE ONLY: never imported by ``mvsnet_amd``.  Parity unpinned by the
+(train.py:428-429); further down the recurrent regulariser with its classification loss, the UNetDS2GN towers and the
+regression loss (loss.py:31-92, 134-220), which tests/train_reference.py composes into whole training steps.
+TEST INFRASTRUCTURE ONLY: never imported by ``mvsnet_amd``.  Parity unpinned by the
 reference (no tests / fixtures there; see mvsnet_oracle.py header); the forward value of this file is
 checked against the strict numpy restatement in tests/test_cpu_restatement.py.
 """
@@ -65,14 +67,16 @@ def _bn_relu(x, p, eps=1e-5):
     return F.relu(F.batch_norm(x, None, None, p["gamma"], p["beta"], training=True, eps=eps))
 
 
-def regnet_us0(cost, p):
+def regnet_us0(cost, p, bn_relu=None):
     """cost (C,D,H,W) -> (D,H,W), or a batch (B,C,D,H,W) -> (B,D,H,W) whose BatchNorm statistics run over the whole
     batch (what cross-replica BatchNorm computes with one sample per replica); p[name] = {'w','gamma','beta'} tensors
-    in the TensorFlow layouts."""
+    in the TensorFlow layouts.  `bn_relu(name, x, p[name])`: what normalises and rectifies layer `name` (default: _bn_relu;
+    tests/train_reference.py records the pre-activations through it)."""
     batched = cost.dim() == 5
     x = cost if batched else cost[None]
-    cb = lambda t, n, s: _bn_relu(_conv(t, p[n]["w"], s), p[n])
-    db = lambda t, n: _bn_relu(_deconv(t, p[n]["w"]), p[n])
+    act = bn_relu or (lambda _n, t, q: _bn_relu(t, q))
+    cb = lambda t, n, s: act(n, _conv(t, p[n]["w"], s), p[n])
+    db = lambda t, n: act(n, _deconv(t, p[n]["w"]), p[n])
     c1_0 = cb(x, "3dconv1_0", 2); c2_0 = cb(c1_0, "3dconv2_0", 2); c3_0 = cb(c2_0, "3dconv3_0", 2)
     c0_1 = cb(x, "3dconv0_1", 1); c1_1 = cb(c1_0, "3dconv1_1", 1); c2_1 = cb(c2_0, "3dconv2_1", 1)
     c3_1 = cb(c3_0, "3dconv3_1", 1)
@@ -90,9 +94,9 @@ def soft_argmin(reg, depth_start, depth_interval):
     return (P * z[:, None, None]).sum(0)
 
 
-def depth_from_features(features, t8, depth_start, depth_interval, p):
+def depth_from_features(features, t8, depth_start, depth_interval, p, bn_relu=None):
     """features (N,H,W,C), t8 (N-1,D,8) -> depth (H,W), differentiable in features and p."""
-    return soft_argmin(regnet_us0(cost_volume(features, t8), p), depth_start, depth_interval)
+    return soft_argmin(regnet_us0(cost_volume(features, t8), p, bn_relu), depth_start, depth_interval)
 
 
 # ---- recurrent regulariser (model.py:505-599) and classification loss (loss.py:223-267) ------------------------
@@ -221,3 +225,70 @@ def unet_ds2gn_gradients(images, params, g, dtype=torch.float64, layer=unet_laye
     f = unet_ds2gn(mk(images), p, layer)
     (f * mk(g)).sum().backward()
     return f.detach().numpy(), {(name, key): t.grad.numpy() for name, d in p.items() for key, t in d.items()}
+
+
+# ---- regression loss (loss.py:31-92, 134-220) --------------------------------------------------------------------------
+# Written from the reference, NOT from mvsnet_amd/loss.py (the code under test in tests/test_gpu_train_step.py); dtype-generic
+# like the towers above.
+
+def power_loss(y_true, y_pred, interval, alpha, beta):
+    """loss.py:31-92 (no_interval_norm=False): 10 mean_true^beta / interval^alpha x the sum over valid pixels of
+    (|y_true - y_pred| + 0.005 y_true)^alpha / (y_true^beta x number of valid pixels); (B,H,W,1) -> (B,)."""
+    mask = (y_true != 0).to(y_pred.dtype)                                   # :56
+    num_valid = mask.sum(dim=(1, 2, 3)).abs() + 1e-6                        # :58-59
+    if beta == 0.0:                                                        # :62-67
+        denominator = num_valid.view(-1, 1, 1, 1)
+    else:
+        denominator = torch.pow(y_true + 1e-9, beta) * num_valid.view(-1, 1, 1, 1)
+    numerator = (y_true - y_pred).abs() + 0.005 * y_true                   # :70-71
+    if alpha != 1.0:
+        numerator = torch.pow(numerator, alpha)                            # :72-74
+    loss = (numerator * mask / denominator).sum(dim=(1, 2, 3))              # :76-78
+    mean_true = (y_true * mask).sum() / num_valid                           # :81-82
+    return loss * (10.0 * torch.pow(mean_true, beta) / torch.pow(interval.view(-1), alpha))     # :87-89
+
+
+def gradient_loss_terms(y_true, y_pred):
+    """The arguments of the two log(1 + .) sums of loss.py:134-158 BEFORE the absolute value, their pair masks and the mask.  The reference
+    slices the first two axes of whatever it is given -- for the (B,H,W,1) batch the "vertical" term differences the batch axis
+    (empty below three samples) and the "horizontal" one the image rows; reproduced as written."""
+    mask = (y_true != 0).to(y_pred.dtype)                                   # :140
+    diff = y_true - y_pred                                                 # :142
+    v_mask, h_mask = mask[0:-2, :] * mask[2:, :], mask[:, 0:-2] * mask[:, 2:]           # :145, :149
+    v = (diff[0:-2, :] - diff[2:, :]) * v_mask                             # :144-146
+    h = (diff[:, 0:-2] - diff[:, 2:]) * h_mask                             # :148-150
+    return v, h, v_mask, h_mask, mask
+
+
+def gradient_loss(y_true, y_pred):
+    """loss.py:134-158 with log=True."""
+    v, h, _vm, _hm, mask = gradient_loss_terms(y_true, y_pred)
+    return (torch.log(1.0 + v.abs()).sum() + torch.log(1.0 + h.abs()).sum()) / mask.sum()       # :152-158
+
+
+def regression_loss(est, gt, depth_start, depth_end, loss_type="power", alpha=0.25, beta=0.0, grad_loss=True):
+    """mvsnet_regression_loss (loss.py:189-220) on est, gt (B,H,W,1) in est's dtype: (loss, less_one, less_three, debug),
+    differentiable in est.  interval = (end - start) / 191 whatever the number of planes (:194); 'original' (:15-28) and 'power'
+    losses; the gradient loss enters with 0.5 (:208-210).  The reference adds the scalar gradient loss to a per-sample vector;
+    the sum over the samples returned here is that vector's only entry at batch size one, the size the trainer runs."""
+    dt = est.dtype
+    as_t = lambda v: torch.as_tensor(np.asarray(v, np.float64).reshape(-1)).to(dt)
+    gt = gt.to(dt)
+    interval = (as_t(depth_end) - as_t(depth_start)) / 191.0                 # :194
+    mask = (gt != 0).to(dt)
+    if loss_type == "original":                                            # :15-28
+        denom = mask.sum(dim=(1, 2, 3)).abs() + 1e-6
+        loss = (((mask * (gt - est)).abs().sum(dim=(1, 2, 3)) / interval) / denom).sum()
+    elif loss_type == "power":
+        loss = power_loss(gt, est, interval, alpha, beta).sum()
+    else:
+        raise NotImplementedError(loss_type)
+    debug = None
+    if grad_loss:
+        debug = gradient_loss(gt, est)
+        loss = loss + 0.5 * debug                                          # :208-210
+    rel = (gt - est).abs() / interval.view(-1, 1, 1, 1)                    # :168-170
+    denom = mask.sum().abs() + 1e-6
+    less_one = (mask * (rel <= 1.0).to(dt)).sum() / denom                   # :171-173
+    less_three = (mask * (rel <= 3.0).to(dt)).sum() / denom                 # :185-187
+    return loss, less_one, less_three, debug
