@@ -825,6 +825,44 @@ int mvs_raster_mesh_f32(const float* vertices, int M, const int* faces, int F, c
 int mvs_raster_interpolate_f32(const float* vertices, int M, const int* faces, int F, const float* proj, int V, int H, int W,
                                float min_depth, const int* index, const float* attr, int C, float* out, void* stream);
 
+/* Connected components of a triangle mesh, their measures, and the compaction of a selection of them (csrc/mesh_components.hip;
+ * semantics in mvsnet_amd/mesh_clean.py).  M vertices and F faces, each 0..2^31-1 (negative: MVS_E_BADARG, beyond: MVS_E_SHAPE);
+ * a pointer to an array of M or F entries may be NULL when that size is 0.
+ *   vertices      (M,3) float32, read only; a face with a non-finite vertex is invalid
+ *   faces         (F,3) int32; a face that names a vertex outside 0..M-1 is invalid and never dereferenced
+ *   workspace     mvs_mesh_components_workspace_bytes(M, F) bytes (0 for invalid sizes): 64 int32 status words, then the
+ *                 union-find parents and the smallest index under each root.  Status word 0 is the error word (non-zero: a lane ran past the cap on walk steps and
+ *                 retries, the result is void), word 1 the number of invalid faces, word 2 the number of unreferenced vertices
+ * mvs_mesh_components_label_i32 clears the status words and writes
+ *   vertex_labels (M) int32: the smallest vertex index of the vertex's component
+ *   face_labels   (F) int32: the label of the face's first vertex, -1 for an invalid face
+ * mvs_mesh_components_measure_f32 takes the labels and the workspace as the label call left them and writes
+ *   counts        (M) int32: at index L the number of faces of label L (0 where L is no label, or that of an unreferenced vertex)
+ *   boxes         (M,6) uint32: at row L the minima (x, y, z) and maxima (x, y, z) over the vertices of component L as ordered
+ *                 images of their float32 bits (bits ^ 0x80000000 for a clear sign bit, ~bits otherwise); 0xffffffff and 0 where
+ *                 the component has no face
+ * mvs_mesh_compact_mark_i32: keep_label (M) int32, non-zero at the labels to keep ->
+ *   face_keep     (F) int32: 1 for a face whose label is kept, else 0
+ *   vertex_keep   (M) int32: 1 for a vertex that a kept face names, else 0
+ * mvs_mesh_compact_write_f32: face_rank and vertex_rank are the inclusive prefix sums of face_keep and vertex_keep, F_out and
+ * M_out their last entries -> out_vertices (M_out,3), out_colours (M_out,3) (colours and out_colours NULL together),
+ * out_faces (F_out,3) re-indexed, all in input order.
+ * All four only enqueue on `stream`: nothing is allocated, nothing synchronised.  The only atomics on outputs are integer sums,
+ * minima and maxima, so the same inputs give the same bytes in any order and grid.  Every argument is checked before the first
+ * GPU call (MVS_E_BADARG, MVS_E_SHAPE, MVS_E_WORKSPACE) and the outputs are untouched on error. */
+size_t mvs_mesh_components_workspace_bytes(long long M, long long F);
+int mvs_mesh_components_label_i32(const float* vertices, long long M, const int* faces, long long F, int* vertex_labels,
+                                  int* face_labels, void* workspace, size_t workspace_bytes, void* stream);
+int mvs_mesh_components_measure_f32(const float* vertices, long long M, long long F, const int* vertex_labels,
+                                    const int* face_labels, int* counts, unsigned int* boxes, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int mvs_mesh_compact_mark_i32(const int* faces, long long M, long long F, const int* face_labels, const int* keep_label,
+                              int* face_keep, int* vertex_keep, void* stream);
+int mvs_mesh_compact_write_f32(const float* vertices, const unsigned char* colours, long long M, const int* faces, long long F,
+                               const int* face_keep, const int* face_rank, const int* vertex_keep, const int* vertex_rank,
+                               long long M_out, long long F_out, float* out_vertices, unsigned char* out_colours, int* out_faces,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

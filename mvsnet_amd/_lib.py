@@ -18,6 +18,7 @@ _i = C.c_int
 _p = C.c_void_p
 _sz = C.c_size_t
 _pp = C.POINTER(C.c_void_p)
+_ll = C.c_longlong
 
 # name -> (restype, argtypes); must list every symbol include/mvsnet_hip.h declares
 SIGNATURES = {
@@ -141,6 +142,11 @@ SIGNATURES = {
     "mvs_raster_workspace_bytes": (_sz, [_i] * 4),
     "mvs_raster_mesh_f32": (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _i, _f, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "mvs_raster_interpolate_f32": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _f, _p, _p, _i, _p, _p]),
+    "mvs_mesh_components_workspace_bytes": (_sz, [_ll, _ll]),
+    "mvs_mesh_components_label_i32": (_i, [_p, _ll, _p, _ll, _p, _p, _p, _sz, _p]),
+    "mvs_mesh_components_measure_f32": (_i, [_p, _ll, _ll, _p, _p, _p, _p, _p, _sz, _p]),
+    "mvs_mesh_compact_mark_i32": (_i, [_p, _ll, _ll, _p, _p, _p, _p, _p]),
+    "mvs_mesh_compact_write_f32": (_i, [_p, _p, _ll, _p, _ll, _p, _p, _p, _p, _ll, _ll, _p, _p, _p, _p]),
 }
 
 CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}

@@ -15,6 +15,7 @@ With --fusion hip, steps 2 and 3 are replaced by this project's own geometric-co
 points_mvsnet/consistencyCheck-<YYYYmmdd-HHMMSS>/final3d_model.ply, the path the reference's scripts look for:
     python -m mvsnet_amd.depthfusion --dense_folder <dir> --fusion hip [--reproj_threshold 1.0]
         [--depth_rel_threshold 0.01] [--no_dedupe] [--fusion_sources {all,listed}] [--mesh]
+        [--mesh_min_component_faces 0] [--mesh_min_component_extent 0] [--mesh_keep_largest 0]
         [--eval_gt G.ply [--eval_max_dist 20] [--eval_thresholds 0.5,1,2]]
         [--normals] [--normal_angle_threshold DEG] [--jump_threshold 0.05] [--write_normal_maps]
 --normals estimates surface normals from the depth maps on the GPU and writes the PLY as x y z nx ny nz red green blue
@@ -138,12 +139,13 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
 
 def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent,
                dedupe=True, fusion_sources="all", eval_gt=None, eval_max_dist=20.0, eval_thresholds=(), normals=False,
-               normal_angle_threshold=None, jump_threshold=0.05, write_normal_maps=False, mesh=False):
+               normal_angle_threshold=None, jump_threshold=0.05, write_normal_maps=False, mesh=False, mesh_clean=None):
     """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply
     (with normals: x y z nx ny nz red green blue; write_normal_maps: depths_mvsnet/<idx>_normal.pfm, camera frame).
     With eval_gt (a PLY), the fused cloud is evaluated against it on the device (mvsnet_amd.evaluate) and the metrics are
     written to metrics.json next to the PLY.  With mesh, mvsnet_amd.mesh writes mesh.ply beside it: TSDF fusion and surface
-    nets of the same depth maps under the same consistency criteria."""
+    nets of the same depth maps under the same consistency criteria; mesh_clean = dict(min_component_faces=,
+    min_component_extent=, keep_largest=) removes its small pieces (mvsnet_amd.mesh_clean)."""
     import json
     import time
     from . import fusion
@@ -177,7 +179,7 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
         from .mesh import mesh_dense_folder
         print("meshed: %s" % json.dumps(mesh_dense_folder(
             dense_folder, os.path.join(out, "mesh.ply"), fusion_sources=fusion_sources, prob_threshold=prob_threshold,
-            reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent)))
+            reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent, **(mesh_clean or {}))))
     return path
 
 
@@ -221,7 +223,17 @@ def main(argv=None):
                     help="--fusion hip: write depths_mvsnet/<idx>_normal.pfm (colour PFM, camera frame)")
     ap.add_argument("--mesh", action="store_true",
                     help="--fusion hip: also write mesh.ply beside final3d_model.ply (mvsnet_amd.mesh, default options)")
+    from .mesh_clean import add_options, check_options
+    add_options(ap, "mesh_")
     a = ap.parse_args(argv)
+    try:
+        clean = check_options(a.mesh_min_component_faces, a.mesh_min_component_extent, a.mesh_keep_largest)
+    except ValueError as e:
+        raise SystemExit("--mesh_min_component_faces and --mesh_keep_largest must be integers >= 0, --mesh_min_component_extent "
+                         "finite and >= 0 (%s)" % e)
+    for flag, given in zip(("--mesh_min_component_faces", "--mesh_min_component_extent", "--mesh_keep_largest"), clean):
+        if given and not a.mesh:
+            raise SystemExit("%s needs --mesh" % flag)
     if a.fusion != "hip":
         for flag, given in (("--mesh", a.mesh), ("--normals", a.normals), ("--normal_angle_threshold", a.normal_angle_threshold is not None),
                             ("--jump_threshold", a.jump_threshold is not None), ("--write_normal_maps", a.write_normal_maps)):
@@ -258,7 +270,8 @@ def main(argv=None):
                           eval_max_dist=a.eval_max_dist, eval_thresholds=eval_thresholds, normals=a.normals,
                           normal_angle_threshold=a.normal_angle_threshold,
                           jump_threshold=0.05 if a.jump_threshold is None else a.jump_threshold,
-                          write_normal_maps=a.write_normal_maps, mesh=a.mesh)
+                          write_normal_maps=a.write_normal_maps, mesh=a.mesh,
+                          mesh_clean=dict(min_component_faces=clean[0], min_component_extent=clean[1], keep_largest=clean[2]))
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")

@@ -3,6 +3,7 @@ mesh by naive surface nets, the last stage between the depth maps and a model th
 
     python -m mvsnet_amd.mesh --dense_folder DIR [--out mesh.ply] [--voxel S | --resolution R] [--bounds x0:y0:z0:x1:y1:z1]
         [--trunc_voxels 4] [--prob_threshold 0.8] [--num_consistent 3] [--min_count 1] [--fusion_sources all|listed] [--force]
+        [--min_component_faces 0] [--min_component_extent 0] [--keep_largest 0]
 
 The kernels are csrc/tsdf.hip (mvs_tsdf_integrate_f32, mvs_surface_nets_count_f32, mvs_surface_nets_write_f32); torch owns the
 device memory and the two scans between counting and writing.
@@ -45,6 +46,10 @@ The mesh of a session (``mesh_depth_maps``, the command line): the depth maps ar
 geometric-consistency fusion keeps (``consistency_masks``: fusion.py's criteria without dedupe), which removes the outliers
 the probability filter lets through; num_consistent = 0 leaves the probability filter alone.  Default bounds are the box of
 the fusion's kept points, widened by trunc plus one voxel.
+
+Small pieces: with min_component_faces, min_component_extent or keep_largest non-zero the extracted mesh goes through
+mvsnet_amd.mesh_clean (its docstring has the semantics) on the device, before the copy to the host; with all three at 0
+nothing of it runs and the mesh is the extraction's, byte for byte.
 """
 from __future__ import annotations
 
@@ -271,11 +276,16 @@ class TsdfVolume:
             _lib.check(rc, "mvs_tsdf_integrate_f32")
         return self
 
-    def extract(self, min_count=1):
-        """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation."""
+    def extract(self, min_count=1, clean=None):
+        """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation.  With
+        clean = dict(min_faces=, min_extent=, keep_largest=) the mesh goes through mesh_clean.clean_mesh on the device before
+        the copy to the host and the result is (vertices, colours, faces, report)."""
         import torch
         from . import _lib
         min_count = check_min_count(min_count)
+        if clean is not None:
+            from . import mesh_clean
+            clean = mesh_clean.check_options(**clean)                          # before any GPU work
         lib = _lib.load()
         nx, ny, nz = self.dims
         nodes = nx * ny * nz
@@ -303,7 +313,11 @@ class TsdfVolume:
                     self.voxel, nx, ny, nz, min_count, _lib.ptr(cell_rank), _lib.ptr(face_end), M, F, _lib.ptr(vertices),
                     _lib.ptr(colours), _lib.ptr(faces) if F else None, _lib.ptr(ws), wsb, _lib.stream_ptr())
                 _lib.check(rc, "mvs_surface_nets_write_f32")
-            return vertices.cpu().numpy(), colours.cpu().numpy(), faces.cpu().numpy()
+            report = None
+            if clean is not None:
+                vertices, colours, faces, report = mesh_clean.clean_device(vertices, colours, faces, self.dev, *clean)
+            mesh = (vertices.cpu().numpy(), colours.cpu().numpy(), faces.cpu().numpy())
+            return mesh if clean is None else mesh + (report,)
 
     def tsdf(self):
         """For inspection -> (f (nz,ny,nx) float32 = sum / count, NaN where count is 0, count (nz,ny,nx) int32) as numpy."""
@@ -337,12 +351,22 @@ def consistency_masks(depths, probs, cams, **options):
     return _consistency(depths, probs, cams, **options)[0]
 
 
-def mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution=None, bounds=None, trunc_voxels=4,
-                    num_consistent=3, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, sources=None,
-                    min_count=1, device=None):
+def mesh_depth_maps(depths, probs, cams, images=None, **options):
     """V depth maps -> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32).  Give a voxel or a resolution (nodes
-    along the longest axis, 256 when neither is given); bounds (lo, hi) default to the box of the consistent points."""
+    along the longest axis, 256 when neither is given); bounds (lo, hi) default to the box of the consistent points.  Options:
+    voxel, resolution, bounds, trunc_voxels, num_consistent, prob_threshold, reproj_threshold, depth_rel_threshold, sources,
+    min_count, device, and min_component_faces, min_component_extent, keep_largest (all 0: no cleaning runs)."""
+    return _mesh_depth_maps(depths, probs, cams, images, **options)[:3]
+
+
+def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution=None, bounds=None, trunc_voxels=4,
+                     num_consistent=3, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, sources=None,
+                     min_count=1, device=None, min_component_faces=0, min_component_extent=0.0, keep_largest=0):
+    """mesh_depth_maps -> (vertices, colours, faces, the cleaning's report or None)."""
+    from . import mesh_clean
     from .fusion import FusionPlan
+    clean = mesh_clean.check_options(min_component_faces, min_component_extent, keep_largest)
+    clean = dict(zip(mesh_clean.OPTION_NAMES, clean)) if mesh_clean.wanted(*clean) else None
     if voxel is not None and resolution is not None:
         raise ValueError("give a voxel or a resolution, not both")
     tv = float(trunc_voxels)
@@ -370,7 +394,9 @@ def mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution=
         origin, voxel, dims = choose_volume(bounds[0], bounds[1], voxel, resolution)
     vol = TsdfVolume(origin, voxel, dims, tv * voxel, colour=images is not None, device=device)
     vol.integrate(depths, probs, cams, images, prob_threshold=prob_threshold)
-    return vol.extract(min_count)
+    if clean is None:
+        return vol.extract(min_count) + (None,)
+    return vol.extract(min_count, clean=clean)
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -390,6 +416,8 @@ def build_parser():
     ap.add_argument("--fusion_sources", choices=("all", "listed"), default="all",
                     help="consistency against every other view, or the neighbours of pair.txt / covisibility.json")
     ap.add_argument("--force", action="store_true", help="overwrite an existing output file")
+    from .mesh_clean import add_options
+    add_options(ap)
     return ap
 
 
@@ -407,6 +435,13 @@ def parse_args(argv=None):
             raise ValueError("--resolution must be at least 2, got %r" % (a.resolution,))
         if math.isnan(a.prob_threshold) or not a.num_consistent >= 0:
             raise ValueError("--prob_threshold must be a number and --num_consistent >= 0")
+        from .mesh_clean import check_options
+        try:
+            a.min_component_faces, a.min_component_extent, a.keep_largest = check_options(a.min_component_faces,
+                                                                                          a.min_component_extent, a.keep_largest)
+        except ValueError as e:
+            raise ValueError("--min_component_faces and --keep_largest must be integers >= 0, --min_component_extent finite "
+                             "and >= 0 (%s)" % e)
     except ValueError as e:
         raise SystemExit("mvsnet_amd.mesh: %s" % e)
     if a.out is None:
@@ -426,10 +461,13 @@ def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", **options):
     from . import fusion
     indices, depths, probs, cams, images = fusion.load_dense_folder(dense_folder)
     sources = fusion.listed_sources(dense_folder, indices) if fusion_sources == "listed" else None
-    vertices, colours, faces = mesh_depth_maps(depths, probs, cams, images, sources=sources, **options)
+    vertices, colours, faces, cleaned = _mesh_depth_maps(depths, probs, cams, images, sources=sources, **options)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     write_mesh_ply(out, vertices, colours, faces)
-    return {"views": len(indices), "vertices": int(len(vertices)), "faces": int(len(faces)), "out": out}
+    report = {"views": len(indices), "vertices": int(len(vertices)), "faces": int(len(faces)), "out": out}
+    if cleaned is not None:
+        report.update(cleaned)                                                 # the cleaning's fields (mesh_clean.py, Report)
+    return report
 
 
 def main(argv=None):
@@ -442,7 +480,9 @@ def main(argv=None):
     try:
         report = mesh_dense_folder(a.dense_folder, out, fusion_sources=a.fusion_sources, voxel=a.voxel, resolution=a.resolution,
                                    bounds=a.bounds, trunc_voxels=a.trunc_voxels, num_consistent=a.num_consistent,
-                                   prob_threshold=a.prob_threshold, min_count=a.min_count)
+                                   prob_threshold=a.prob_threshold, min_count=a.min_count,
+                                   min_component_faces=a.min_component_faces, min_component_extent=a.min_component_extent,
+                                   keep_largest=a.keep_largest)
     except (ValueError, OSError) as e:
         raise SystemExit("mvsnet_amd.mesh: %s" % e)
     print(json.dumps(report))
