@@ -17,6 +17,24 @@
  *     mvs_profile_layers_ms (wait for their timing events);
  *   - return value: 0 on success, a positive hipError_t on a HIP failure, a negative
  *     MVS_E_* code on an argument error.  Nothing throws.
+ *
+ * Memory contract of the hot path (homographies, warp, cost volume, the 3-D convolutions, RegNetUS0, soft-argmin, the ConvGRU
+ * stages and the recurrent sweep, the 2-D tower layers and the training kernels; tests/test_gpu_arena.py runs each of them with
+ * every operand in one poisoned, guarded arena, tests/device_arena.py):
+ *   - alignment: 16 bytes for every tensor, statistics, prepared-weight and workspace pointer is enough for every entry point
+ *     (the kernels move channel quads as 16-byte packets and float64 sums as 8-byte words).  Nothing needs more: a workspace is
+ *     carved at 256-byte multiples of ITS OWN start, whatever that is, and no kernel assumes the 256 or 512 bytes an allocator
+ *     usually gives.  Only mvs_center_images_u8_f32 checks its pointers (images 4 bytes, out4 16: MVS_E_SHAPE);
+ *   - every element of every output is written by the call, whatever the output held before -- except where an argument is
+ *     documented as an accumulator the caller clears (the float64 `stats` / `sums` / `stats_out`, the gradients of
+ *     mvs_cost_volume_bwd_f32, the running maps of mvs_wta_update_f32) or as updated in place (`h` of mvs_gru_blend_f32);
+ *   - scratch holds anything on entry: workspaces (exactly mvs_*_workspace_bytes() bytes suffice), and the transforms / cost /
+ *     reg buffers of mvs_depth_from_features_f32, are written before they are read, so one workspace may serve calls of
+ *     changing shape back to back on a stream, and NaN or stale values left in it change nothing;
+ *   - nothing outside the stated extents is written: not a byte before or after an output or a workspace, and inputs, weights
+ *     and affines are never modified.  A call refused with MVS_E_WORKSPACE has enqueued nothing and written nothing;
+ *   - the result does not depend on what lies outside the inputs: SAME padding and out-of-image taps are zeros (or clamped
+ *     taps) formed by the kernels, and no load leaves a tensor's extent.
  */
 #ifndef MVSNET_HIP_H_
 #define MVSNET_HIP_H_
