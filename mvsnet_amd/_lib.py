@@ -221,6 +221,28 @@ def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def gpu_ready():
+    """None when the HIP library loads and a GPU is visible, else the reason."""
+    try:
+        load()
+    except Exception as e:                     # library missing or not loadable
+        return str(e)
+    if not torch.cuda.is_available():
+        return "no GPU is visible to this process"
+    return None
+
+
+def device(device, what):
+    """The torch device a GPU-only stage runs on: ``device`` (None: the current one) with its index filled in.  ``what`` names
+    the stage in the error text ("TSDF fusion", ...)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda")
+    if dev.type != "cuda":
+        raise ValueError("%s runs on a GPU device, got %s" % (what, dev))
+    if not torch.cuda.is_available():
+        raise MvsnetHipError("%s runs on the GPU (HIP); no GPU is visible to this process" % what)
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
 import threading
 
 _GRU_LOCK = threading.Lock()   # the table below is touched from garbage-collection finalizers as well

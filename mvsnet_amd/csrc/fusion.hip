@@ -38,26 +38,18 @@
 // template parameter.
 // The compiler merges some neighbouring stores into wide ones; tools/store_hazard_scan.py (run by the CPU suite) finds none of
 // them with its data registers overwritten too early.
-#include "common.h"
+#include "geom_common.h"
 
 namespace {
 
 constexpr int FU_THREADS = 256;
 constexpr int FU_TABLE = 12;          // floats per 3x4 matrix
 constexpr int FU_MAX_SLICES = 16;
-constexpr int FU_CHUNK = 1024;        // pixels per compaction block (4 per thread)
+constexpr int FU_CHUNK = FU_THREADS * GEO_COMPACT_PER;   // 1024 pixels per compaction block
 #ifndef FU_NSTRIDE
 #define FU_NSTRIDE 4                  // floats per pixel of the internal normal map (EXPERIMENTS.md: 4 padded, 3 packed)
 #endif
 static_assert(FU_NSTRIDE == 3 || FU_NSTRIDE == 4, "internal normal map: 3 (packed) or 4 (padded, validity word) floats per pixel");
-
-__global__ __launch_bounds__(FU_THREADS) void fusion_filter_kernel(const float* __restrict__ depth, const float* __restrict__ prob,
-                                                                    size_t n, float thr, float* __restrict__ df) {
-    const size_t i = (size_t)blockIdx.x * FU_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const float d = depth[i], p = prob[i];
-    df[i] = (d > 0.f && __builtin_isfinite(d) && p >= thr) ? d : 0.f;
-}
 
 __device__ __forceinline__ void fu_apply(const float* __restrict__ m, float a0, float a1, float a2, float& o0, float& o1, float& o2) {
     o0 = fmaf(m[0], a0, fmaf(m[1], a1, fmaf(m[2], a2, m[3])));
@@ -65,16 +57,13 @@ __device__ __forceinline__ void fu_apply(const float* __restrict__ m, float a0, 
     o2 = fmaf(m[8], a0, fmaf(m[9], a1, fmaf(m[10], a2, m[11])));
 }
 
-// Wave-uniform, read-only data through the scalar unit: a load from the constant address space at a uniform address is an
-// s_load (a plain global pointer would be loaded per lane: the compiler cannot prove the memory unclobbered).
-typedef __attribute__((address_space(4))) const float fu_cfloat;
-typedef __attribute__((address_space(4))) const int fu_cint;
+typedef __attribute__((address_space(4))) const int fu_cint;       // geo_cfloat's sibling: scalar loads of uniform ints
 
 struct FuMat { float m[FU_TABLE]; };
 
 // Matrix `index` (wave-uniform; readfirstlane states it to the compiler) of a table of 3x4 matrices.
 __device__ __forceinline__ FuMat fu_load_mat(const float* table, int index) {
-    const fu_cfloat* c = (const fu_cfloat*)table + (size_t)__builtin_amdgcn_readfirstlane(index) * FU_TABLE;
+    const geo_cfloat* c = (const geo_cfloat*)table + (size_t)__builtin_amdgcn_readfirstlane(index) * FU_TABLE;
     FuMat t;
 #pragma unroll
     for (int i = 0; i < FU_TABLE; ++i) t.m[i] = c[i];
@@ -115,7 +104,7 @@ struct FuNrm {
 };
 __device__ __forceinline__ const FuNrm& fu_nrm(const FuNrm& a) { return a; }
 
-// Filtered depth of element i: from df, or (RAW) from depth and prob by the rule of fusion_filter_kernel.
+// Filtered depth of element i: from df, or (RAW) from depth and prob by the rule of geo_filter_kernel.
 template <bool RAW>
 __device__ __forceinline__ float fu_filtered(const float* __restrict__ depth, const float* __restrict__ prob, float thr, size_t i) {
     const float d = depth[i];
@@ -344,49 +333,6 @@ __global__ __launch_bounds__(FU_THREADS) void fusion_finalize_kernel(
     }
 }
 
-// Exclusive scan of one value per thread over a 256-thread block (Hillis-Steele in LDS); returns the thread's prefix.
-__device__ int fu_block_exclusive_scan(int v, int* sh, int& total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < FU_THREADS; o <<= 1) {
-        const int add = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    total = sh[FU_THREADS - 1];
-    const int incl = sh[t];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ __launch_bounds__(FU_THREADS) void fusion_count_kernel(const uint8_t* __restrict__ keep, size_t n, int* __restrict__ counts) {
-    __shared__ int sh[FU_THREADS];
-    const size_t e0 = (size_t)blockIdx.x * FU_CHUNK + 4 * threadIdx.x;
-    int c = 0;
-    for (int i = 0; i < 4; ++i) c += (e0 + i < n && keep[e0 + i]) ? 1 : 0;
-    int total;
-    fu_block_exclusive_scan(c, sh, total);
-    if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-// One workgroup: exclusive scan of the nb block counts into offs, the total into *count.
-__global__ __launch_bounds__(FU_THREADS) void fusion_scan_kernel(const int* __restrict__ counts, int nb, int* __restrict__ offs,
-                                                                  int* __restrict__ count) {
-    __shared__ int sh[FU_THREADS];
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += FU_THREADS) {
-        const int b = b0 + threadIdx.x;
-        const int c = b < nb ? counts[b] : 0;
-        int total;
-        const int ex = fu_block_exclusive_scan(c, sh, total);
-        if (b < nb) offs[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) *count = carry;
-}
-
 template <bool NRM, typename... NA>
 __global__ __launch_bounds__(FU_THREADS) void fusion_write_kernel(
         const uint8_t* __restrict__ keep, const float* __restrict__ fxyz, size_t n, int HW, int W, const int* __restrict__ offs,
@@ -396,12 +342,12 @@ __global__ __launch_bounds__(FU_THREADS) void fusion_write_kernel(
     float* __restrict__ normals = nullptr;
     if constexpr (NRM) { fnrm = fu_nrm(na...).fnrm; normals = fu_nrm(na...).normals; }
     __shared__ int sh[FU_THREADS];
-    const size_t e0 = (size_t)blockIdx.x * FU_CHUNK + 4 * threadIdx.x;
+    const size_t e0 = (size_t)blockIdx.x * FU_CHUNK + GEO_COMPACT_PER * threadIdx.x;
     int c = 0;
-    for (int i = 0; i < 4; ++i) c += (e0 + i < n && keep[e0 + i]) ? 1 : 0;
+    for (int i = 0; i < GEO_COMPACT_PER; ++i) c += (e0 + i < n && keep[e0 + i]) ? 1 : 0;
     int total;
-    int o = offs[blockIdx.x] + fu_block_exclusive_scan(c, sh, total);
-    for (int i = 0; i < 4; ++i) {
+    int o = offs[blockIdx.x] + geo_block_exclusive_scan<FU_THREADS>(c, sh, total);
+    for (int i = 0; i < GEO_COMPACT_PER; ++i) {
         const size_t e = e0 + i;
         if (e >= n || !keep[e]) continue;
         xyz[3 * (size_t)o] = fxyz[3 * e];
@@ -429,8 +375,6 @@ __global__ __launch_bounds__(FU_THREADS) void fusion_write_kernel(
     }
 }
 
-size_t fu_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int fusion_slices(int HW, int max_src, int dedupe) {
     if (!dedupe || max_src <= 1) return 1;
     int s = mvs_cdiv(4096, mvs_cdiv(HW, 64));          // about 4096 waves per view launch
@@ -450,18 +394,18 @@ FuLayout fusion_layout(int V, int H, int W, int max_src, int dedupe, bool normal
     L.slices = fusion_slices((int)HW, max_src, dedupe);
     L.nb = (int)((px + FU_CHUNK - 1) / FU_CHUNK);
     const size_t nview = dedupe ? 1 : (size_t)V;
-    size_t o = 0;
-    L.df = o;      o += fu_align(px * sizeof(float));
-    L.used = o;    o += dedupe ? fu_align(px) : 0;
-    L.part = o;    o += fu_align((size_t)L.slices * (normals ? 7 : 4) * nview * HW * sizeof(float));
-    L.witness = o; o += dedupe ? fu_align((size_t)max_src * HW * sizeof(int)) : 0;
-    L.keep = o;    o += fu_align(px);
-    L.fxyz = o;    o += fu_align(px * 3 * sizeof(float));
-    L.counts = o;  o += fu_align((size_t)L.nb * sizeof(int));
-    L.offs = o;    o += fu_align((size_t)L.nb * sizeof(int));
-    L.nmap = o;    o += normals ? fu_align(px * FU_NSTRIDE * sizeof(float)) : 0;
-    L.fnrm = o;    o += normals ? fu_align(px * 3 * sizeof(float)) : 0;
-    L.total = o;
+    GeoCarver c;
+    L.df = c.take(px * sizeof(float));
+    L.used = c.take(dedupe ? px : 0);
+    L.part = c.take((size_t)L.slices * (normals ? 7 : 4) * nview * HW * sizeof(float));
+    L.witness = c.take(dedupe ? (size_t)max_src * HW * sizeof(int) : 0);
+    L.keep = c.take(px);
+    L.fxyz = c.take(px * 3 * sizeof(float));
+    L.counts = c.take((size_t)L.nb * sizeof(int));
+    L.offs = c.take((size_t)L.nb * sizeof(int));
+    L.nmap = c.take(normals ? px * FU_NSTRIDE * sizeof(float) : 0);
+    L.fnrm = c.take(normals ? px * 3 * sizeof(float) : 0);
+    L.total = c.off;
     return L;
 }
 
@@ -517,7 +461,7 @@ int fusion_launch(const float* depth, const float* prob, int V, int H, int W, co
     const float reproj2 = reproj_threshold * reproj_threshold;
     const unsigned gx = (unsigned)mvs_cdiv(HW, FU_THREADS);
 
-    hipLaunchKernelGGL(fusion_filter_kernel, dim3((unsigned)((px + FU_THREADS - 1) / FU_THREADS)), dim3(FU_THREADS), 0, st,
+    hipLaunchKernelGGL(geo_filter_kernel<FU_THREADS>, dim3((unsigned)((px + FU_THREADS - 1) / FU_THREADS)), dim3(FU_THREADS), 0, st,
                        depth, prob, px, prob_threshold, df);
     if (NRM)
         hipLaunchKernelGGL((fusion_normal_map_kernel<FU_NSTRIDE, false>), dim3(gx, V), dim3(FU_THREADS), 0, st, df,
@@ -550,8 +494,8 @@ int fusion_launch(const float* depth, const float* prob, int V, int H, int W, co
         pairs(dim3(gx, V, 1), nullptr, 0, nullptr);
         finalize(dim3(gx, V), nullptr, 1, nullptr, 0);
     }
-    hipLaunchKernelGGL(fusion_count_kernel, dim3(L.nb), dim3(FU_THREADS), 0, st, keep, px, counts);
-    hipLaunchKernelGGL(fusion_scan_kernel, dim3(1), dim3(FU_THREADS), 0, st, counts, L.nb, offs, count);
+    hipLaunchKernelGGL(geo_compact_count_kernel<FU_THREADS>, dim3(L.nb), dim3(FU_THREADS), 0, st, keep, px, counts);
+    hipLaunchKernelGGL(geo_scan_top_kernel<FU_THREADS>, dim3(1), dim3(FU_THREADS), 0, st, counts, L.nb, 0, offs, count);
     if constexpr (NRM)
         hipLaunchKernelGGL((fusion_write_kernel<true, FuNrm>), dim3(L.nb), dim3(FU_THREADS), 0, st, keep, fxyz, px, HW, W, offs, images,
                            img_h, img_w, H, xyz, rgb, view_index, pixel_index, na);

@@ -24,7 +24,7 @@
 //   mark       face_keep[f] = keep_label[face_labels[f]] != 0, and plain stores of 1 to vertex_keep at its three vertices;
 //   write      one lane per index: a kept vertex (and its colour) goes to vertex_rank - 1, a kept face to face_rank - 1 with
 //              its indices replaced by vertex_rank - 1.  The two inclusive scans are the caller's.
-#include "common.h"
+#include "geom_common.h"
 
 #define MC_HD __device__ __forceinline__
 #include "mesh_link.h"
@@ -313,7 +313,14 @@ __global__ __launch_bounds__(MC_THREADS) void mc_write_kernel(const float* __res
     }
 }
 
-size_t mc_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// [status words | parent | root_min]
+struct McLayout { size_t status, parent, root_min, total; };
+
+McLayout mc_layout(long long M) {
+    GeoCarver c;
+    const size_t ints = (size_t)std::max(M, 1LL) * sizeof(int);
+    return {c.take(MC_STATUS_WORDS * sizeof(int)), c.take(ints), c.take(ints), c.off};
+}
 
 int mc_sizes(long long M, long long F) {
     if (M < 0 || F < 0) return MVS_E_BADARG;
@@ -325,7 +332,7 @@ int mc_sizes(long long M, long long F) {
 
 extern "C" size_t mvs_mesh_components_workspace_bytes(long long M, long long F) {
     if (mc_sizes(M, F) != 0) return 0;
-    return mc_align(MC_STATUS_WORDS * sizeof(int)) + 2 * mc_align((size_t)std::max(M, 1LL) * sizeof(int));
+    return mc_layout(M).total;
 }
 
 extern "C" int mvs_mesh_components_label_i32(const float* vertices, long long M, const int* faces, long long F, int* vertex_labels,
@@ -333,11 +340,13 @@ extern "C" int mvs_mesh_components_label_i32(const float* vertices, long long M,
     MVS_CHECK_ARG(workspace);
     if (int rc = mc_sizes(M, F)) return rc;
     MVS_CHECK_ARG((M == 0 || (vertices && vertex_labels)) && (F == 0 || (faces && face_labels)));
-    if (workspace_bytes < mvs_mesh_components_workspace_bytes(M, F)) return MVS_E_WORKSPACE;
+    const McLayout L = mc_layout(M);
+    if (workspace_bytes < L.total) return MVS_E_WORKSPACE;
     hipStream_t st = mvs_stream(stream);
-    int* status = static_cast<int*>(workspace);
-    int* parent = reinterpret_cast<int*>(static_cast<char*>(workspace) + mc_align(MC_STATUS_WORDS * sizeof(int)));
-    int* root_min = reinterpret_cast<int*>(reinterpret_cast<char*>(parent) + mc_align((size_t)std::max(M, 1LL) * sizeof(int)));
+    char* ws = static_cast<char*>(workspace);
+    int* status = reinterpret_cast<int*>(ws + L.status);
+    int* parent = reinterpret_cast<int*>(ws + L.parent);
+    int* root_min = reinterpret_cast<int*>(ws + L.root_min);
     hipError_t e = hipMemsetAsync(status, 0, MC_STATUS_WORDS * sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     const dim3 gm(mvs_cdiv(M, MC_THREADS)), gf(mvs_cdiv(F, MC_THREADS)), block(MC_THREADS);
@@ -355,9 +364,10 @@ extern "C" int mvs_mesh_components_measure_f32(const float* vertices, long long 
     MVS_CHECK_ARG(workspace);
     if (int rc = mc_sizes(M, F)) return rc;
     MVS_CHECK_ARG((M == 0 || (vertices && vertex_labels && counts && boxes)) && (F == 0 || face_labels));
-    if (workspace_bytes < mvs_mesh_components_workspace_bytes(M, F)) return MVS_E_WORKSPACE;
+    const McLayout L = mc_layout(M);
+    if (workspace_bytes < L.total) return MVS_E_WORKSPACE;
     hipStream_t st = mvs_stream(stream);
-    int* status = static_cast<int*>(workspace);
+    int* status = reinterpret_cast<int*>(static_cast<char*>(workspace) + L.status);
     const dim3 gm(mvs_cdiv(std::max(M, 1LL), MC_THREADS)), gf(mvs_cdiv(F, MC_THREADS)), block(MC_THREADS);
     hipLaunchKernelGGL(mc_measure_init_kernel, gm, block, 0, st, counts, boxes, M, status);
     if (M && F) hipLaunchKernelGGL(mc_count_kernel, gf, block, 0, st, face_labels, M, F, counts);

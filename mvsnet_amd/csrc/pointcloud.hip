@@ -28,7 +28,7 @@
 // does not move, once; mvs_icp_step_f32 is one pass per iteration, one lane per source point: transform in float64, the
 // query above, the eighteen float64 moments of the correspondences, reduced as the statistics are.  Nothing per point
 // goes to memory unless the caller asks for dist / index.
-#include "common.h"
+#include "geom_common.h"
 
 namespace {
 
@@ -38,7 +38,7 @@ constexpr int PC_SCAN_CHUNK = PC_THREADS * PC_SCAN_PER;   // 4096
 constexpr long long PC_MAX_CELLS = 1LL << 24;
 constexpr int PC_MAX_THRESHOLDS = 16;
 constexpr int PC_STATS_BLOCKS = 1024;
-constexpr int PC_COMPACT_CHUNK = 1024;                    // points per compaction block (4 per thread)
+constexpr int PC_COMPACT_CHUNK = PC_THREADS * GEO_COMPACT_PER;   // 1024 points per compaction block
 constexpr float PC_EPS_REL = 8e-6f;                       // bound deflation, relative to the coordinate scale
 constexpr float PC_SHRINK = 1.0f - 1e-5f;                 // bound deflation of squared distances (float32 d^2 rounding)
 
@@ -72,22 +72,6 @@ __global__ __launch_bounds__(PC_THREADS) void pc_scatter_kernel(const float* __r
 // ------------------------------------------------------------------ multi-block exclusive scan of int arrays, in place
 // grid (chunks, arrays): array y at data + y * stride (m entries), its chunk totals at bsum + y * bstride.
 
-__device__ int pc_block_exclusive_scan(int v, int* sh, int& total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < PC_THREADS; o <<= 1) {
-        const int add = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    total = sh[PC_THREADS - 1];
-    const int incl = sh[t];
-    __syncthreads();
-    return incl - v;
-}
-
 __global__ __launch_bounds__(PC_THREADS) void pc_scan_reduce_kernel(const int* __restrict__ data, int m, size_t stride,
                                                                      int* __restrict__ bsum, int bstride) {
     __shared__ int sh[PC_THREADS];
@@ -96,23 +80,8 @@ __global__ __launch_bounds__(PC_THREADS) void pc_scan_reduce_kernel(const int* _
     int s = 0;
     for (int k = 0; k < PC_SCAN_PER; ++k) s += e0 + k < m ? d[e0 + k] : 0;
     int total;
-    pc_block_exclusive_scan(s, sh, total);
+    geo_block_exclusive_scan<PC_THREADS>(s, sh, total);
     if (threadIdx.x == 0) bsum[blockIdx.y * bstride + blockIdx.x] = total;
-}
-
-// One workgroup per array: exclusive scan of the nb chunk totals in place.
-__global__ __launch_bounds__(PC_THREADS) void pc_scan_top_kernel(int* __restrict__ bsum, int nb, int bstride) {
-    __shared__ int sh[PC_THREADS];
-    int* b = bsum + blockIdx.y * bstride;
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += PC_THREADS) {
-        const int k = b0 + threadIdx.x;
-        const int c = k < nb ? b[k] : 0;
-        int total;
-        const int ex = pc_block_exclusive_scan(c, sh, total);
-        if (k < nb) b[k] = carry + ex;
-        carry += total;
-    }
 }
 
 __global__ __launch_bounds__(PC_THREADS) void pc_scan_apply_kernel(int* __restrict__ data, int m, size_t stride,
@@ -128,7 +97,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_scan_apply_kernel(int* __restri
         s += v[k];
     }
     int total;
-    int o = bsum[blockIdx.y * bstride + blockIdx.x] + pc_block_exclusive_scan(s, sh, total);
+    int o = bsum[blockIdx.y * bstride + blockIdx.x] + geo_block_exclusive_scan<PC_THREADS>(s, sh, total);
 #pragma unroll
     for (int k = 0; k < PC_SCAN_PER; ++k) {
         if (e0 + k < m) d[e0 + k] = o;
@@ -413,27 +382,17 @@ __global__ __launch_bounds__(PC_THREADS) void pc_voxel_mark_kernel(const long lo
     keep[o] = (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(PC_THREADS) void pc_compact_count_kernel(const uint8_t* __restrict__ keep, int n, int* __restrict__ counts) {
-    __shared__ int sh[PC_THREADS];
-    const long long e0 = (long long)blockIdx.x * PC_COMPACT_CHUNK + 4 * threadIdx.x;
-    int c = 0;
-    for (int k = 0; k < 4; ++k) c += (e0 + k < n && keep[e0 + k]) ? 1 : 0;
-    int total;
-    pc_block_exclusive_scan(c, sh, total);
-    if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
 __global__ __launch_bounds__(PC_THREADS) void pc_compact_write_kernel(const uint8_t* __restrict__ keep, const float* __restrict__ xyz,
                                                                        int n, const int* __restrict__ offs, int nb,
                                                                        float* __restrict__ out, int* __restrict__ count) {
     __shared__ int sh[PC_THREADS];
-    const long long e0 = (long long)blockIdx.x * PC_COMPACT_CHUNK + 4 * threadIdx.x;
+    const long long e0 = (long long)blockIdx.x * PC_COMPACT_CHUNK + GEO_COMPACT_PER * threadIdx.x;
     int c = 0;
-    for (int k = 0; k < 4; ++k) c += (e0 + k < n && keep[e0 + k]) ? 1 : 0;
+    for (int k = 0; k < GEO_COMPACT_PER; ++k) c += (e0 + k < n && keep[e0 + k]) ? 1 : 0;
     int total;
-    int o = offs[blockIdx.x] + pc_block_exclusive_scan(c, sh, total);
+    int o = offs[blockIdx.x] + geo_block_exclusive_scan<PC_THREADS>(c, sh, total);
     if (blockIdx.x == 0 && threadIdx.x == 0) *count = offs[nb];
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < GEO_COMPACT_PER; ++k) {
         const long long e = e0 + k;
         if (e >= n || !keep[e]) continue;
         out[3 * (size_t)o] = xyz[3 * e];
@@ -445,8 +404,6 @@ __global__ __launch_bounds__(PC_THREADS) void pc_compact_write_kernel(const uint
 
 // ------------------------------------------------------------------ host side
 
-size_t pc_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int pc_scan_chunks(long long m) { return (int)((m + PC_SCAN_CHUNK - 1) / PC_SCAN_CHUNK); }
 
 // Exclusive scan of `arrays` int arrays of m entries each, `stride` apart, in place; bsum: arrays * (chunks + 1) ints.
@@ -454,7 +411,7 @@ hipError_t pc_scan(int* data, long long m, size_t stride, int arrays, int* bsum,
     const int nb = pc_scan_chunks(m);
     const int bstride = nb + 1;
     hipLaunchKernelGGL(pc_scan_reduce_kernel, dim3(nb, arrays), dim3(PC_THREADS), 0, st, data, (int)m, stride, bsum, bstride);
-    hipLaunchKernelGGL(pc_scan_top_kernel, dim3(1, arrays), dim3(PC_THREADS), 0, st, bsum, nb, bstride);
+    hipLaunchKernelGGL(geo_scan_top_kernel<PC_THREADS>, dim3(1, arrays), dim3(PC_THREADS), 0, st, bsum, nb, bstride, bsum, (int*)nullptr);
     hipLaunchKernelGGL(pc_scan_apply_kernel, dim3(nb, arrays), dim3(PC_THREADS), 0, st, data, (int)m, stride, bsum, bstride);
     return hipGetLastError();
 }
@@ -467,17 +424,17 @@ struct NnLayout {
 NnLayout nn_layout(int nq, int nt, long long ncell) {
     NnLayout L{};
     const long long m = ncell + 1;
-    L.stride = pc_align((size_t)m * sizeof(int)) / sizeof(int);
-    size_t o = 0;
-    L.starts = o;  o += 2 * L.stride * sizeof(int);
-    L.bsum = o;    o += pc_align(2 * ((size_t)pc_scan_chunks(m) + 1) * sizeof(int));
-    L.tcell = o;   o += pc_align((size_t)nt * sizeof(int));
-    L.trank = o;   o += pc_align((size_t)nt * sizeof(int));
-    L.qcell = o;   o += pc_align((size_t)nq * sizeof(int));
-    L.qrank = o;   o += pc_align((size_t)nq * sizeof(int));
-    L.tsorted = o; o += pc_align((size_t)nt * sizeof(float4));
-    L.qsorted = o; o += pc_align((size_t)nq * sizeof(float4));
-    L.total = o;
+    L.stride = geo_align256((size_t)m * sizeof(int)) / sizeof(int);
+    GeoCarver c;
+    L.starts = c.take(2 * L.stride * sizeof(int));
+    L.bsum = c.take(2 * ((size_t)pc_scan_chunks(m) + 1) * sizeof(int));
+    L.tcell = c.take((size_t)nt * sizeof(int));
+    L.trank = c.take((size_t)nt * sizeof(int));
+    L.qcell = c.take((size_t)nq * sizeof(int));
+    L.qrank = c.take((size_t)nq * sizeof(int));
+    L.tsorted = c.take((size_t)nt * sizeof(float4));
+    L.qsorted = c.take((size_t)nq * sizeof(float4));
+    L.total = c.off;
     return L;
 }
 
@@ -489,14 +446,14 @@ int stats_blocks(int n) { return (int)std::min<long long>(PC_STATS_BLOCKS, ((lon
 
 size_t stats_bytes(int n) {
     const size_t nb = (size_t)stats_blocks(n);
-    return pc_align(nb * sizeof(double)) + pc_align(nb * (1 + PC_MAX_THRESHOLDS) * sizeof(int));
+    return geo_align256(nb * sizeof(double)) + geo_align256(nb * (1 + PC_MAX_THRESHOLDS) * sizeof(int));
 }
 
 int compact_blocks(int n) { return (int)(((long long)n + PC_COMPACT_CHUNK - 1) / PC_COMPACT_CHUNK); }
 
 size_t voxel_select_bytes(int n) {
     const int nb = compact_blocks(n);
-    return pc_align((size_t)n) + pc_align(((size_t)nb + 1) * sizeof(int)) + pc_align(((size_t)pc_scan_chunks(nb + 1) + 1) * sizeof(int));
+    return geo_align256((size_t)n) + geo_align256(((size_t)nb + 1) * sizeof(int)) + geo_align256(((size_t)pc_scan_chunks(nb + 1) + 1) * sizeof(int));
 }
 
 // The target alone: per-cell starts, scan scratch, per-point cell and rank (kept: they locate a point in the sorted copy), sorted copy.
@@ -505,19 +462,19 @@ struct TargetLayout { size_t starts, bsum, tcell, trank, tsorted, total; };
 TargetLayout target_layout(int nt, long long ncell) {
     TargetLayout L{};
     const long long m = ncell + 1;
-    size_t o = 0;
-    L.starts = o;  o += pc_align((size_t)m * sizeof(int));
-    L.bsum = o;    o += pc_align(((size_t)pc_scan_chunks(m) + 1) * sizeof(int));
-    L.tcell = o;   o += pc_align((size_t)nt * sizeof(int));
-    L.trank = o;   o += pc_align((size_t)nt * sizeof(int));
-    L.tsorted = o; o += pc_align((size_t)nt * sizeof(float4));
-    L.total = o;
+    GeoCarver c;
+    L.starts = c.take((size_t)m * sizeof(int));
+    L.bsum = c.take(((size_t)pc_scan_chunks(m) + 1) * sizeof(int));
+    L.tcell = c.take((size_t)nt * sizeof(int));
+    L.trank = c.take((size_t)nt * sizeof(int));
+    L.tsorted = c.take((size_t)nt * sizeof(float4));
+    L.total = c.off;
     return L;
 }
 
 int icp_blocks(int n) { return (int)std::min<long long>(PC_ICP_BLOCKS, ((long long)n + PC_THREADS - 1) / PC_THREADS); }
 
-size_t icp_bytes(int n) { return pc_align((size_t)icp_blocks(n) * PC_ICP_MOMENTS * sizeof(double)); }
+size_t icp_bytes(int n) { return geo_align256((size_t)icp_blocks(n) * PC_ICP_MOMENTS * sizeof(double)); }
 
 }  // namespace
 
@@ -671,7 +628,7 @@ extern "C" int mvs_dist_stats_f32(const float* dist, int n, float max_dist, cons
     const int nb = stats_blocks(n);
     char* ws = static_cast<char*>(workspace);
     double* psum = reinterpret_cast<double*>(ws);
-    int* pcnt = reinterpret_cast<int*>(ws + pc_align((size_t)nb * sizeof(double)));
+    int* pcnt = reinterpret_cast<int*>(ws + geo_align256((size_t)nb * sizeof(double)));
     hipLaunchKernelGGL(pc_stats_partial_kernel, dim3(nb), dim3(PC_THREADS), 0, st, dist, n, max_dist, thr, n_thresholds, psum, pcnt);
     hipLaunchKernelGGL(pc_stats_final_kernel, dim3(1), dim3(PC_THREADS), 0, st, psum, pcnt, nb, n_thresholds, out);
     MVS_LAUNCH_RET();
@@ -698,12 +655,12 @@ extern "C" int mvs_voxel_select_f32(const float* xyz, int n, const long long* so
     const int nb = compact_blocks(n);
     char* ws = static_cast<char*>(workspace);
     uint8_t* keep = reinterpret_cast<uint8_t*>(ws);
-    int* offs = reinterpret_cast<int*>(ws + pc_align((size_t)n));
-    int* bsum = reinterpret_cast<int*>(ws + pc_align((size_t)n) + pc_align(((size_t)nb + 1) * sizeof(int)));
+    int* offs = reinterpret_cast<int*>(ws + geo_align256((size_t)n));
+    int* bsum = reinterpret_cast<int*>(ws + geo_align256((size_t)n) + geo_align256(((size_t)nb + 1) * sizeof(int)));
     hipError_t e = hipMemsetAsync(offs + nb, 0, sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(pc_voxel_mark_kernel, dim3(mvs_cdiv(n, PC_THREADS)), dim3(PC_THREADS), 0, st, sorted_keys, order, n, keep);
-    hipLaunchKernelGGL(pc_compact_count_kernel, dim3(nb), dim3(PC_THREADS), 0, st, keep, n, offs);
+    hipLaunchKernelGGL(geo_compact_count_kernel<PC_THREADS>, dim3(nb), dim3(PC_THREADS), 0, st, keep, (size_t)n, offs);
     e = pc_scan(offs, (long long)nb + 1, 0, 1, bsum, st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(pc_compact_write_kernel, dim3(nb), dim3(PC_THREADS), 0, st, keep, xyz, n, offs, nb, out, count);

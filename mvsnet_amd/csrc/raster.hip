@@ -20,7 +20,7 @@
 //             channel ((t_a A_a + t_b A_b) + t_c A_c) / ((t_a + t_b) + t_c) in float64.
 // Every float operation is rounded on its own (contraction off); the only atomics on the output are unsigned minima, so no
 // byte depends on the order of execution, the grid, the processing order, large_pixels or queue_capacity.
-#include "common.h"
+#include "geom_common.h"
 
 namespace {
 
@@ -32,7 +32,6 @@ constexpr int RS_MAX_AXIS = 1 << 20;            // H, W: 256 x stays inside the 
 constexpr int RS_MAX_CHANNELS = 8;
 constexpr float RS_GUARD = 268435456.f;         // 2^28, in 1/256 pixel
 constexpr size_t RS_HEAD_BYTES = 256;           // the queue counter, in a block of its own at the workspace's start
-constexpr unsigned long long RS_EMPTY = ~0ull;
 
 // One face in one view after the setup: corners in 1/256 pixel, their depths, sign of the area, clipped bounding box.
 struct RsTri {
@@ -43,17 +42,11 @@ struct RsTri {
     int x0, x1, y0, y1;
 };
 
-// ((P0 x + P1 y) + P2 z) + P3 in float32, every product and sum rounded.
-__device__ __forceinline__ float rs_row(const float* __restrict__ r, const float* p) {
-#pragma clang fp contract(off)
-    return ((r[0] * p[0] + r[1] * p[1]) + r[2] * p[2]) + r[3];
-}
-
 // Projects and snaps one vertex; false when it is unusable in this view (then qx = qy = 0).
 __device__ __forceinline__ bool rs_vertex(const float* __restrict__ P, const float* p, float min_depth, int& qx, int& qy, float& w) {
 #pragma clang fp contract(off)
-    const float u = rs_row(P, p), v = rs_row(P + 4, p);
-    w = rs_row(P + 8, p);
+    const float u = geo_row(P, p[0], p[1], p[2]), v = geo_row(P + 4, p[0], p[1], p[2]);
+    w = geo_row(P + 8, p[0], p[1], p[2]);
     const float fx = floorf(__fdiv_rn(u, w) * 256.f + 0.5f), fy = floorf(__fdiv_rn(v, w) * 256.f + 0.5f);
     // compared in float32, before any conversion; a NaN fails every comparison
     const bool ok = __builtin_isfinite(w) && w > min_depth && fabsf(fx) <= RS_GUARD && fabsf(fy) <= RS_GUARD;
@@ -127,7 +120,7 @@ __device__ __forceinline__ unsigned long long rs_key(const RsTri& t, long long e
     double ta, tb, tc;
     const double s = rs_weights(t, ea, eb, ec, ta, tb, tc);
     const float z = (float)((double)t.area / s);
-    return ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)f;
+    return geo_key(z, f);
 }
 
 // grid (blocks over the faces, chunks of views): lane L of a row of blocks takes faces order[L], order[L + lanes], ...
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_small_kernel(const float* __res
                 for (int k = 0; k < RS_VIEWS; ++k) {
                     long long ea, eb, ec;
                     const bool hit = act[k] && rs_cover(t[k], cx[k], cy[k], ea, eb, ec);
-                    key[k] = RS_EMPTY;
+                    key[k] = GEO_EMPTY;
                     if (hit) key[k] = rs_key(t[k], ea, eb, ec, f);
                     // a lane without a hit loads key 0 of the buffer and masks it to 0: no key is smaller, no atomic follows
                     at[k] = hit ? (size_t)(vb + k) * plane + (size_t)cy[k] * W + cx[k] : (size_t)0;
@@ -224,16 +217,6 @@ __global__ __launch_bounds__(RS_THREADS) void rs_large_kernel(const float* __res
     }
 }
 
-// One lane per pixel of all views.  index may be NULL.
-__global__ __launch_bounds__(RS_THREADS) void rs_resolve_kernel(const unsigned long long* __restrict__ keys, long long pixels,
-                                                                 float* __restrict__ depth, int* __restrict__ index) {
-    const long long p = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
-    if (p >= pixels) return;
-    const unsigned long long k = keys[p];
-    depth[p] = k == RS_EMPTY ? 0.f : __uint_as_float((unsigned)(k >> 32));
-    if (index) index[p] = k == RS_EMPTY ? -1 : (int)(unsigned)k;
-}
-
 // One lane per pixel of all views: C channels of the face its index names, 0 for an empty pixel, an index outside 0..F-1
 // or a face that is dropped in the view.
 __global__ __launch_bounds__(RS_THREADS) void rs_interpolate_kernel(const float* __restrict__ vertices, int M,
@@ -269,23 +252,20 @@ __global__ __launch_bounds__(RS_THREADS) void rs_interpolate_kernel(const float*
         if (c < C) out[(size_t)pix * C + c] = res[c];
 }
 
-size_t rs_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-bool rs_shape_ok(int V, int H, int W) {
-    return H <= RS_MAX_AXIS && W <= RS_MAX_AXIS && (long long)V * H * W <= 0x7fffffffLL;
-}
-
 // [counter block | keys | queue]
-size_t rs_bytes(long long pixels, int queue_capacity) {
-    return RS_HEAD_BYTES + rs_align((size_t)pixels * sizeof(unsigned long long)) +
-           rs_align((size_t)queue_capacity * sizeof(unsigned long long));
+struct RsLayout { size_t counter, keys, queue, total; };
+
+RsLayout rs_layout(long long pixels, int queue_capacity) {
+    GeoCarver c;
+    return {c.take(RS_HEAD_BYTES), c.take((size_t)pixels * sizeof(unsigned long long)),
+            c.take((size_t)queue_capacity * sizeof(unsigned long long)), c.off};
 }
 
 }  // namespace
 
 extern "C" size_t mvs_raster_workspace_bytes(int V, int H, int W, int queue_capacity) {
-    if (V <= 0 || H <= 0 || W <= 0 || queue_capacity < 0 || !rs_shape_ok(V, H, W)) return 0;
-    return rs_bytes((long long)V * H * W, queue_capacity);
+    if (V <= 0 || H <= 0 || W <= 0 || queue_capacity < 0 || !geo_pixels_ok(V, H, W, RS_MAX_AXIS)) return 0;
+    return rs_layout((long long)V * H * W, queue_capacity).total;
 }
 
 extern "C" int mvs_raster_mesh_f32(const float* vertices, int M, const int* faces, int F, const int* order, const float* proj, int V,
@@ -295,29 +275,27 @@ extern "C" int mvs_raster_mesh_f32(const float* vertices, int M, const int* face
     MVS_CHECK_ARG(M > 0 && F > 0 && V > 0 && H > 0 && W > 0);
     MVS_CHECK_ARG(min_depth >= 0.f && __builtin_isfinite(min_depth));
     MVS_CHECK_ARG(cull >= -1 && cull <= 1 && large_pixels >= 0 && queue_capacity >= 0);
-    if (!rs_shape_ok(V, H, W)) return MVS_E_SHAPE;
+    if (!geo_pixels_ok(V, H, W, RS_MAX_AXIS)) return MVS_E_SHAPE;
     const long long pixels = (long long)V * H * W;
-    if (workspace_bytes < rs_bytes(pixels, queue_capacity)) return MVS_E_WORKSPACE;
+    const RsLayout L = rs_layout(pixels, queue_capacity);
+    if (workspace_bytes < L.total) return MVS_E_WORKSPACE;
     hipStream_t st = mvs_stream(stream);
     char* ws = static_cast<char*>(workspace);
-    unsigned long long* counter = reinterpret_cast<unsigned long long*>(ws);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + RS_HEAD_BYTES);
-    unsigned long long* queue = reinterpret_cast<unsigned long long*>(ws + RS_HEAD_BYTES + rs_align((size_t)pixels * sizeof(unsigned long long)));
+    unsigned long long* counter = reinterpret_cast<unsigned long long*>(ws + L.counter);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + L.keys);
+    unsigned long long* queue = reinterpret_cast<unsigned long long*>(ws + L.queue);
 
     hipError_t e = hipMemsetAsync(counter, 0, RS_HEAD_BYTES, st);
     if (e != hipSuccess) return (int)e;
     e = hipMemsetAsync(keys, 0xff, (size_t)pixels * sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
-    // a fixed grid striding over the faces; a small mesh leaves blocks over, which then share the views
-    const int bx = (int)std::min<long long>(RS_BLOCKS, mvs_cdiv(F, RS_THREADS));
-    const int chunks = std::min(V, std::max(1, RS_BLOCKS / bx));
-    const int per = mvs_cdiv(V, chunks);
-    hipLaunchKernelGGL(rs_small_kernel, dim3(bx, mvs_cdiv(V, per)), dim3(RS_THREADS), 0, st, vertices, M, faces, F, order, proj, V, per,
-                       H, W, min_depth, cull, (long long)large_pixels, queue_capacity, keys, counter, queue);
+    const GeoViewGrid g = geo_view_grid(F, V, RS_THREADS, RS_BLOCKS);
+    hipLaunchKernelGGL(rs_small_kernel, dim3(g.blocks, g.chunks), dim3(RS_THREADS), 0, st, vertices, M, faces, F, order, proj, V,
+                       g.per, H, W, min_depth, cull, (long long)large_pixels, queue_capacity, keys, counter, queue);
     if (queue_capacity > 0)
         hipLaunchKernelGGL(rs_large_kernel, dim3(std::min(RS_LARGE_BLOCKS, queue_capacity)), dim3(RS_THREADS), 0, st, vertices, M, faces,
                            F, proj, V, H, W, min_depth, cull, queue_capacity, keys, counter, queue);
-    hipLaunchKernelGGL(rs_resolve_kernel, dim3(mvs_cdiv(pixels, RS_THREADS)), dim3(RS_THREADS), 0, st, keys, pixels, depth, index);
+    hipLaunchKernelGGL(geo_resolve_kernel<RS_THREADS>, dim3(mvs_cdiv(pixels, RS_THREADS)), dim3(RS_THREADS), 0, st, keys, pixels, depth, index);
     MVS_LAUNCH_RET();
 }
 
@@ -328,7 +306,7 @@ extern "C" int mvs_raster_interpolate_f32(const float* vertices, int M, const in
     MVS_CHECK_ARG(M > 0 && F > 0 && V > 0 && H > 0 && W > 0);
     MVS_CHECK_ARG(min_depth >= 0.f && __builtin_isfinite(min_depth));
     MVS_CHECK_ARG(C >= 1 && C <= RS_MAX_CHANNELS);
-    if (!rs_shape_ok(V, H, W)) return MVS_E_SHAPE;
+    if (!geo_pixels_ok(V, H, W, RS_MAX_AXIS)) return MVS_E_SHAPE;
     const long long pixels = (long long)V * H * W;
     hipLaunchKernelGGL(rs_interpolate_kernel, dim3(mvs_cdiv(pixels, RS_THREADS)), dim3(RS_THREADS), 0, mvs_stream(stream), vertices,
                        M, faces, F, proj, pixels, H, W, min_depth, index, attr, C, out);

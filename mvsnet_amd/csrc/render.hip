@@ -15,7 +15,7 @@
 //   filter    optional hidden-point removal: resolve writes the raw map into the workspace, and a second kernel reads a
 //             32 x 8 tile of it with a halo of k pixels into LDS, counts per pixel the window pixels in front of it
 //             (raw[q] > 0 and raw[q] < z * ratio) and writes depth / index; the raw map is only read, so this is order-free.
-#include "common.h"
+#include "geom_common.h"
 
 namespace {
 
@@ -26,19 +26,6 @@ constexpr int RD_MAX_SPLAT = 32;
 constexpr int RD_MAX_OCCL_RADIUS = 16;
 constexpr int RD_MAX_AXIS = 1 << 24;            // H, W: every pixel coordinate is an exact float32
 constexpr int RD_TILE_W = 32, RD_TILE_H = 8;    // filter tile = one workgroup
-constexpr unsigned long long RD_EMPTY = ~0ull;
-
-// ((P0 x + P1 y) + P2 z) + P3 in float32, every product and sum rounded (mvsnet_amd/render.py).
-__device__ __forceinline__ float rd_row(const float* __restrict__ r, float x, float y, float z) {
-#pragma clang fp contract(off)
-    return ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
-}
-
-// floor(a / b + 1/2): correctly rounded division, then one rounded sum.
-__device__ __forceinline__ float rd_pixel(float a, float b) {
-#pragma clang fp contract(off)
-    return floorf(__fdiv_rn(a, b) + 0.5f);
-}
 
 // grid (blocks over the points, chunks of views): lane L of a row of blocks takes points order[L], order[L + lanes], ...
 __global__ __launch_bounds__(RD_THREADS) void rd_splat_kernel(const float* __restrict__ xyz, int n, const int* __restrict__ order,
@@ -62,11 +49,11 @@ __global__ __launch_bounds__(RD_THREADS) void rd_splat_kernel(const float* __res
             for (int k = 0; k < RD_VIEWS; ++k) {
                 const int v = min(vb + k, v1 - 1);                     // wave-uniform: P arrives by scalar loads
                 const float* __restrict__ P = proj + 12 * (size_t)v;
-                const float w = rd_row(P + 8, x, y, z);
-                fx[k] = rd_pixel(rd_row(P, x, y, z), w);
-                fy[k] = rd_pixel(rd_row(P + 4, x, y, z), w);
-                ok[k] = vb + k < v1 && w > min_depth && __builtin_isfinite(w) && __builtin_isfinite(fx[k]) && __builtin_isfinite(fy[k]);
-                key[k] = ((unsigned long long)__float_as_uint(w) << 32) | (unsigned)s;
+                const float w = geo_row(P + 8, x, y, z);
+                fx[k] = geo_pixel(geo_row(P, x, y, z), w);
+                fy[k] = geo_pixel(geo_row(P + 4, x, y, z), w);
+                ok[k] = vb + k < v1 && GEO_USABLE(w, fx[k], fy[k], min_depth);
+                key[k] = geo_key(w, s);
             }
             for (int dy = -splat; dy <= splat; ++dy)
                 for (int dx = -splat; dx <= splat; ++dx) {
@@ -76,7 +63,7 @@ __global__ __launch_bounds__(RD_THREADS) void rd_splat_kernel(const float* __res
                     for (int k = 0; k < RD_VIEWS; ++k) {
                         const float px = fx[k] + (float)dx, py = fy[k] + (float)dy;
                         // in float, before any conversion: a huge coordinate is never converted
-                        const bool in = ok[k] && px >= 0.f && px <= wmax && py >= 0.f && py <= hmax;
+                        const bool in = ok[k] && GEO_INSIDE(px, py, wmax, hmax);
                         // a culled lane loads key 0 of the buffer instead (a load without a branch) and masks it to 0: no
                         // key is smaller than 0, so no atomic follows
                         at[k] = in ? (size_t)(vb + k) * plane + (size_t)(int)py * W + (int)px : (size_t)0;
@@ -92,20 +79,6 @@ __global__ __launch_bounds__(RD_THREADS) void rd_splat_kernel(const float* __res
                 }
         }
     }
-}
-
-__device__ __forceinline__ float rd_key_depth(unsigned long long k) {
-    return k == RD_EMPTY ? 0.f : __uint_as_float((unsigned)(k >> 32));
-}
-
-// One lane per pixel of all views.  depth: the output map, or the raw map of the filter.  index may be NULL.
-__global__ __launch_bounds__(RD_THREADS) void rd_resolve_kernel(const unsigned long long* __restrict__ keys, long long pixels,
-                                                                 float* __restrict__ depth, int* __restrict__ index) {
-    const long long p = (long long)blockIdx.x * RD_THREADS + threadIdx.x;
-    if (p >= pixels) return;
-    const unsigned long long k = keys[p];
-    depth[p] = rd_key_depth(k);
-    if (index) index[p] = k == RD_EMPTY ? -1 : (int)(unsigned)k;
 }
 
 // One workgroup per 32 x 8 tile of one view; tile (tx + k2) x (ty + k2) of the raw map in LDS, 0 outside the image (a zero
@@ -141,21 +114,19 @@ __global__ __launch_bounds__(RD_THREADS) void rd_filter_kernel(const float* __re
     if (index && removed) index[p] = -1;
 }
 
-size_t rd_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// [keys | raw map of the filter]
+struct RdLayout { size_t keys, raw, total; };
 
-bool rd_shape_ok(int V, int H, int W) {
-    return H <= RD_MAX_AXIS && W <= RD_MAX_AXIS && (long long)V * H * W <= 0x7fffffffLL;
-}
-
-size_t rd_bytes(long long pixels, bool occlusion) {
-    return rd_align((size_t)pixels * sizeof(unsigned long long)) + (occlusion ? rd_align((size_t)pixels * sizeof(float)) : 0);
+RdLayout rd_layout(long long pixels, bool occlusion) {
+    GeoCarver c;
+    return {c.take((size_t)pixels * sizeof(unsigned long long)), c.take(occlusion ? (size_t)pixels * sizeof(float) : 0), c.off};
 }
 
 }  // namespace
 
 extern "C" size_t mvs_render_workspace_bytes(int V, int H, int W, int occlusion) {
-    if (V <= 0 || H <= 0 || W <= 0 || !rd_shape_ok(V, H, W)) return 0;
-    return rd_bytes((long long)V * H * W, occlusion != 0);
+    if (V <= 0 || H <= 0 || W <= 0 || !geo_pixels_ok(V, H, W, RD_MAX_AXIS)) return 0;
+    return rd_layout((long long)V * H * W, occlusion != 0).total;
 }
 
 extern "C" int mvs_render_points_f32(const float* xyz, int n, const int* order, const float* proj, int V, int H, int W, int splat,
@@ -168,23 +139,21 @@ extern "C" int mvs_render_points_f32(const float* xyz, int n, const int* order, 
     MVS_CHECK_ARG(occl_radius >= 0 && occl_radius <= RD_MAX_OCCL_RADIUS);
     const bool occlusion = occl_radius > 0;
     if (occlusion) MVS_CHECK_ARG(occl_ratio > 0.f && occl_ratio < 1.f && occl_count >= 1);
-    if (!rd_shape_ok(V, H, W)) return MVS_E_SHAPE;
+    if (!geo_pixels_ok(V, H, W, RD_MAX_AXIS)) return MVS_E_SHAPE;
     const long long pixels = (long long)V * H * W;
-    if (workspace_bytes < rd_bytes(pixels, occlusion)) return MVS_E_WORKSPACE;
+    const RdLayout L = rd_layout(pixels, occlusion);
+    if (workspace_bytes < L.total) return MVS_E_WORKSPACE;
     hipStream_t st = mvs_stream(stream);
     char* ws = static_cast<char*>(workspace);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
-    float* raw = reinterpret_cast<float*>(ws + rd_align((size_t)pixels * sizeof(unsigned long long)));
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + L.keys);
+    float* raw = reinterpret_cast<float*>(ws + L.raw);
 
     hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)pixels * sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
-    // a fixed grid striding over the points; a small cloud leaves blocks over, which then share the views
-    const int bx = (int)std::min<long long>(RD_BLOCKS, mvs_cdiv(n, RD_THREADS));
-    const int chunks = std::min(V, std::max(1, RD_BLOCKS / bx));
-    const int per = mvs_cdiv(V, chunks);
-    hipLaunchKernelGGL(rd_splat_kernel, dim3(bx, mvs_cdiv(V, per)), dim3(RD_THREADS), 0, st, xyz, n, order, proj, V, per, H, W,
+    const GeoViewGrid g = geo_view_grid(n, V, RD_THREADS, RD_BLOCKS);
+    hipLaunchKernelGGL(rd_splat_kernel, dim3(g.blocks, g.chunks), dim3(RD_THREADS), 0, st, xyz, n, order, proj, V, g.per, H, W,
                        splat, min_depth, keys);
-    hipLaunchKernelGGL(rd_resolve_kernel, dim3(mvs_cdiv(pixels, RD_THREADS)), dim3(RD_THREADS), 0, st, keys, pixels,
+    hipLaunchKernelGGL(geo_resolve_kernel<RD_THREADS>, dim3(mvs_cdiv(pixels, RD_THREADS)), dim3(RD_THREADS), 0, st, keys, pixels,
                        occlusion ? raw : depth, index);
     if (occlusion) {
         const int tiles_x = mvs_cdiv(W, RD_TILE_W), tiles_y = mvs_cdiv(H, RD_TILE_H);

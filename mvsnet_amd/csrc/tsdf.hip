@@ -13,7 +13,7 @@
 //   edges      one lane per node: the number of triangles its three edges give (0, 2, 4 or 6);
 //   write      one lane per node: the vertex of its cell when active, at rank - 1 of the inclusive scan of the active flags,
 //              and its triangles at the inclusive scan of the counts minus its own count.  The scans are the caller's.
-#include "common.h"
+#include "geom_common.h"
 
 // every product and sum below is rounded on its own: the numpy statement has no fused multiply-add
 #pragma clang fp contract(off)
@@ -25,25 +25,6 @@ constexpr int TS_BX = 64, TS_BY = 4, TS_BZ = 4;    // brick: a wave is one x-row
 constexpr int TS_VIEWS = 4;                        // views a lane works on at once (loads in flight)
 constexpr int TS_MAX_AXIS = 1 << 24;               // H, W, image sizes: every pixel coordinate is an exact float32
 constexpr int TS_CELL_VALID = 1, TS_CELL_ACTIVE = 2;
-
-typedef __attribute__((address_space(4))) const float ts_cfloat;   // wave-uniform reads through the scalar unit (fusion.hip)
-
-__global__ __launch_bounds__(TS_THREADS) void ts_filter_kernel(const float* __restrict__ depth, const float* __restrict__ prob,
-                                                                size_t n, float thr, float* __restrict__ df) {
-    const size_t i = (size_t)blockIdx.x * TS_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const float d = depth[i], p = prob[i];
-    df[i] = (d > 0.f && __builtin_isfinite(d) && p >= thr) ? d : 0.f;
-}
-
-// ((P0 x + P1 y) + P2 z) + P3 in float32, every product and sum rounded (render.hip's rd_row, from the constant space).
-__device__ __forceinline__ float ts_row(ts_cfloat* r, float x, float y, float z) {
-    return ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
-}
-
-__device__ __forceinline__ float ts_pixel(float a, float b) {
-    return floorf(__fdiv_rn(a, b) + 0.5f);
-}
 
 // o + s float(i): a rounded product, then a rounded sum.
 __device__ __forceinline__ float ts_coord(float o, float s, float i) {
@@ -92,13 +73,12 @@ __global__ __launch_bounds__(TS_THREADS) void ts_integrate_kernel(const float* _
             for (int t = 0; t < TS_VIEWS; ++t) {
                 const int v = min(vb + t, V - 1);                              // wave-uniform: P arrives by scalar loads
                 view[t] = v;
-                ts_cfloat* P = (ts_cfloat*)proj + 12 * (size_t)v;
-                w[t] = ts_row(P + 8, x, y, z);
-                fx[t] = ts_pixel(ts_row(P, x, y, z), w[t]);
-                fy[t] = ts_pixel(ts_row(P + 4, x, y, z), w[t]);
+                geo_cfloat* P = (geo_cfloat*)proj + 12 * (size_t)v;                // the constant space: scalar loads
+                w[t] = geo_row(P + 8, x, y, z);
+                fx[t] = geo_pixel(geo_row(P, x, y, z), w[t]);
+                fy[t] = geo_pixel(geo_row(P + 4, x, y, z), w[t]);
                 // in float, before any conversion: a huge or non-finite coordinate is never converted
-                const bool in = column && vb + t < V && __builtin_isfinite(w[t]) && w[t] > 0.f && __builtin_isfinite(fx[t]) &&
-                                __builtin_isfinite(fy[t]) && fx[t] >= 0.f && fx[t] <= wmax && fy[t] >= 0.f && fy[t] <= hmax;
+                const bool in = column && vb + t < V && GEO_VISIBLE(w[t], fx[t], fy[t], 0.f, wmax, hmax);
                 // a culled lane loads element 0 instead (a load without a branch) and masks it to 0, which is "no depth"
                 const size_t at = in ? (size_t)v * plane + (size_t)(int)fy[t] * W + (int)fx[t] : (size_t)0;
                 const float g = df[at];
@@ -296,8 +276,6 @@ __global__ __launch_bounds__(TS_THREADS) void ts_write_kernel(const float* __res
     }
 }
 
-size_t ts_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 bool ts_volume_ok(int nx, int ny, int nz) { return (long long)nx * ny * nz <= 0x7fffffffLL; }
 
 long long ts_cells(int nx, int ny, int nz) { return (long long)(nx - 1) * (ny - 1) * (nz - 1); }
@@ -305,8 +283,8 @@ long long ts_cells(int nx, int ny, int nz) { return (long long)(nx - 1) * (ny - 
 }  // namespace
 
 extern "C" size_t mvs_tsdf_integrate_workspace_bytes(int V, int H, int W) {
-    if (V <= 0 || H <= 0 || W <= 0 || H > TS_MAX_AXIS || W > TS_MAX_AXIS || (long long)V * H * W > 0x7fffffffLL) return 0;
-    return ts_align((size_t)V * H * W * sizeof(float));
+    if (V <= 0 || H <= 0 || W <= 0 || !geo_pixels_ok(V, H, W, TS_MAX_AXIS)) return 0;
+    return geo_align256((size_t)V * H * W * sizeof(float));
 }
 
 extern "C" int mvs_tsdf_integrate_f32(const float* depth, const float* prob, int V, int H, int W, const float* proj,
@@ -320,14 +298,13 @@ extern "C" int mvs_tsdf_integrate_f32(const float* depth, const float* prob, int
     MVS_CHECK_ARG(!__builtin_isnan(prob_threshold) && flags == 0);
     const bool colour = images != nullptr;
     if (colour) MVS_CHECK_ARG(rgb_sum && rgb_count && img_h > 0 && img_w > 0);
-    if (!ts_volume_ok(nx, ny, nz) || H > TS_MAX_AXIS || W > TS_MAX_AXIS || (long long)V * H * W > 0x7fffffffLL)
-        return MVS_E_SHAPE;
+    if (!ts_volume_ok(nx, ny, nz) || !geo_pixels_ok(V, H, W, TS_MAX_AXIS)) return MVS_E_SHAPE;
     if (colour && (img_h > TS_MAX_AXIS || img_w > TS_MAX_AXIS)) return MVS_E_SHAPE;
     const size_t pixels = (size_t)V * H * W;
-    if (workspace_bytes < ts_align(pixels * sizeof(float))) return MVS_E_WORKSPACE;
+    if (workspace_bytes < geo_align256(pixels * sizeof(float))) return MVS_E_WORKSPACE;
     hipStream_t st = mvs_stream(stream);
     float* df = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(ts_filter_kernel, dim3(mvs_cdiv((long long)pixels, TS_THREADS)), dim3(TS_THREADS), 0, st, depth, prob, pixels,
+    hipLaunchKernelGGL(geo_filter_kernel<TS_THREADS>, dim3(mvs_cdiv((long long)pixels, TS_THREADS)), dim3(TS_THREADS), 0, st, depth, prob, pixels,
                        prob_threshold, df);
     const int bx = mvs_cdiv(nx, TS_BX), by = mvs_cdiv(ny, TS_BY), bz = mvs_cdiv(nz, TS_BZ);
     const dim3 grid((unsigned)((long long)bx * by * bz));
@@ -343,7 +320,7 @@ extern "C" int mvs_tsdf_integrate_f32(const float* depth, const float* prob, int
 extern "C" size_t mvs_surface_nets_workspace_bytes(int nx, int ny, int nz) {
     if (nx <= 0 || ny <= 0 || nz <= 0 || !ts_volume_ok(nx, ny, nz)) return 0;
     const long long cells = (nx > 1 && ny > 1 && nz > 1) ? ts_cells(nx, ny, nz) : 0;
-    return ts_align((size_t)std::max(cells, 1LL) * sizeof(int)) + ts_align((size_t)nx * ny * nz * sizeof(int));
+    return geo_align256((size_t)std::max(cells, 1LL) * sizeof(int)) + geo_align256((size_t)nx * ny * nz * sizeof(int));
 }
 
 extern "C" int mvs_surface_nets_count_f32(const float* sum, const int* count, int nx, int ny, int nz, int min_count, int* totals,
@@ -356,7 +333,7 @@ extern "C" int mvs_surface_nets_count_f32(const float* sum, const int* count, in
     const long long nodes = (long long)nx * ny * nz;
     const long long cells = (nx > 1 && ny > 1 && nz > 1) ? ts_cells(nx, ny, nz) : 0;
     int* cell_flags = static_cast<int*>(workspace);
-    int* face_count = reinterpret_cast<int*>(static_cast<char*>(workspace) + ts_align((size_t)std::max(cells, 1LL) * sizeof(int)));
+    int* face_count = reinterpret_cast<int*>(static_cast<char*>(workspace) + geo_align256((size_t)std::max(cells, 1LL) * sizeof(int)));
     hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     if (cells == 0) {                                                          // an axis of one node: no cells, no faces
@@ -388,7 +365,7 @@ extern "C" int mvs_surface_nets_write_f32(const float* sum, const int* count, co
     const long long nodes = (long long)nx * ny * nz;
     const int* cell_flags = static_cast<const int*>(workspace);
     const int* face_count = reinterpret_cast<const int*>(static_cast<const char*>(workspace) +
-                                                         ts_align((size_t)ts_cells(nx, ny, nz) * sizeof(int)));
+                                                         geo_align256((size_t)ts_cells(nx, ny, nz) * sizeof(int)));
     hipStream_t st = mvs_stream(stream);
     const dim3 grid(mvs_cdiv(nodes, TS_THREADS));
     if (rgb_sum)

@@ -1,7 +1,7 @@
 // View selection from cameras and a cloud (mvs_view_visibility_f32, mvs_view_scores_f32, mvs_view_depth_hist_f32).  The
 // semantics are normative in mvsnet_amd/select_views.py; tests/view_selection_reference.py restates them in numpy.
 //
-//   visibility  one lane per point, the view loop inside the lane with P_v's twelve floats in scalar registers: render.hip's
+//   visibility  one lane per point, the view loop inside the lane with P_v's twelve floats in scalar registers: geom_common.h's
 //               float32 projection and pixel, the candidate test, optionally the comparison with a rendered depth map, and
 //               the point's bit of each view.  A lane owns its point's mask words, so it gathers the bits of one word in a
 //               register and ORs the word into memory when the next view falls into another word: no atomics.
@@ -20,7 +20,7 @@
 //               fall into a few dozen of these bins, and global atomics on them would serialise.  Pass 1: one lane per
 //               point, per view with the point's bit set and a high half equal to one of the view's two prefixes an integer
 //               atomic add into the histogram of bits(w) & 0xffff: few points, spread over 65 536 bins.
-#include "common.h"
+#include "geom_common.h"
 
 namespace {
 
@@ -39,16 +39,6 @@ constexpr int VS_BINS = 65536;
 constexpr int VS_LDS_BINS = 32768;              // pass 0 in LDS: the high halves of all non-negative floats, 128 KB of the CU's 160
 constexpr int VS_HIST_THREADS = 1024;
 constexpr int VS_HIST_BLOCKS = 768;             // three rounds of one workgroup per CU
-
-__device__ __forceinline__ float vs_row(const float* __restrict__ r, float x, float y, float z) {
-#pragma clang fp contract(off)
-    return ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
-}
-
-__device__ __forceinline__ float vs_pixel(float a, float b) {
-#pragma clang fp contract(off)
-    return floorf(__fdiv_rn(a, b) + 0.5f);
-}
 
 // (x*x' + y*y') + z*z', every product and sum rounded
 __device__ __forceinline__ float vs_dot(float ax, float ay, float az, float bx, float by, float bz) {
@@ -82,10 +72,9 @@ __global__ __launch_bounds__(VS_THREADS) void vs_visibility_kernel(const float* 
                 word = bit >> 6;
                 bits = 0;
             }
-            const float w = vs_row(P + 8, x, y, z);
-            const float fx = vs_pixel(vs_row(P, x, y, z), w), fy = vs_pixel(vs_row(P + 4, x, y, z), w);
-            bool vis = __builtin_isfinite(w) && w > min_depth && __builtin_isfinite(fx) && __builtin_isfinite(fy) &&
-                       fx >= 0.f && fx <= wmax && fy >= 0.f && fy <= hmax;
+            const float w = geo_row(P + 8, x, y, z);
+            const float fx = geo_pixel(geo_row(P, x, y, z), w), fy = geo_pixel(geo_row(P + 4, x, y, z), w);
+            bool vis = GEO_VISIBLE(w, fx, fy, min_depth, wmax, hmax);
             if (zbuf && vis) {                                       // inside the image: the conversion is exact
                 const float zb = zbuf[(size_t)v * plane + (size_t)(int)fy * W + (int)fx];
                 vis = zb > 0.f && w <= zb * z_tol;
@@ -239,7 +228,7 @@ __global__ __launch_bounds__(VS_THREADS) void vs_depth_hist_kernel(const float* 
         for (int v = 0; v < V; ++v) {
             if ((v & 63) == 0) bits = row[v >> 6];
             if (!((bits >> (v & 63)) & 1ull)) continue;
-            const unsigned w = __float_as_uint(vs_row(proj + 12 * (size_t)v + 8, x, y, z));
+            const unsigned w = __float_as_uint(geo_row(proj + 12 * (size_t)v + 8, x, y, z));
             if (!prefixes) {
                 atomicAdd(hist + (size_t)v * VS_BINS + (w >> 16), 1u);
             } else {
@@ -266,7 +255,7 @@ __global__ __launch_bounds__(VS_HIST_THREADS) void vs_depth_hist_lds_kernel(cons
     unsigned int* __restrict__ out = hist + (size_t)v * VS_BINS;
     for (long long i = (long long)blockIdx.x * VS_HIST_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * VS_HIST_THREADS) {
         if (!((mask[(size_t)i * mask_words + (v >> 6)] >> (v & 63)) & 1ull)) continue;
-        const unsigned high = __float_as_uint(vs_row(P, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2])) >> 16;
+        const unsigned high = __float_as_uint(geo_row(P, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2])) >> 16;
         if (high < (unsigned)VS_LDS_BINS) atomicAdd(&vs_bins[high], 1u);
         else atomicAdd(out + high, 1u);
     }
@@ -277,7 +266,6 @@ __global__ __launch_bounds__(VS_HIST_THREADS) void vs_depth_hist_lds_kernel(cons
     }
 }
 
-size_t vs_align(size_t b) { return (b + 255) & ~(size_t)255; }
 int vs_words(int V) { return (V + 63) / 64; }
 int vs_tiles(int V) { return vs_words(V) * (vs_words(V) + 1) / 2; }
 int vs_grid(int n) { return (int)std::min<long long>(VS_BLOCKS, mvs_cdiv(n, VS_THREADS)); }
@@ -292,7 +280,7 @@ extern "C" int mvs_view_visibility_f32(const float* xyz, int n, const float* pro
     MVS_CHECK_ARG(min_depth >= 0.f && __builtin_isfinite(min_depth));
     if (zbuf) MVS_CHECK_ARG(z_tol >= 1.f && __builtin_isfinite(z_tol));
     if (n < 1 || V > VS_MAX_VIEWS || mask_words < vs_words(V)) return MVS_E_SHAPE;
-    if (H > VS_MAX_AXIS || W > VS_MAX_AXIS || (long long)V * H * W > 0x7fffffffLL) return MVS_E_SHAPE;
+    if (!geo_pixels_ok(V, H, W, VS_MAX_AXIS)) return MVS_E_SHAPE;
     hipLaunchKernelGGL(vs_visibility_kernel, dim3(vs_grid(n)), dim3(VS_THREADS), 0, mvs_stream(stream), xyz, n, proj, view_bits, V,
                        H, W, min_depth, zbuf, z_tol, mask, mask_words);
     MVS_LAUNCH_RET();
@@ -300,7 +288,7 @@ extern "C" int mvs_view_visibility_f32(const float* xyz, int n, const float* pro
 
 extern "C" size_t mvs_view_scores_workspace_bytes(int n, int V) {
     if (n < 1 || V < 1 || V > VS_MAX_VIEWS) return 0;
-    return vs_align((size_t)vs_tiles(V) * sizeof(unsigned int));
+    return geo_align256((size_t)vs_tiles(V) * sizeof(unsigned int));
 }
 
 extern "C" int mvs_view_scores_f32(const float* xyz, int n, const int* order, const unsigned long long* mask, int mask_words,
@@ -310,7 +298,7 @@ extern "C" int mvs_view_scores_f32(const float* xyz, int n, const int* order, co
     MVS_CHECK_ARG(V > 0 && mask_words > 0);
     if (n < 1 || V > VS_MAX_VIEWS || mask_words < vs_words(V)) return MVS_E_SHAPE;
     const int tiles = vs_tiles(V);
-    if (workspace_bytes < vs_align((size_t)tiles * sizeof(unsigned int))) return MVS_E_WORKSPACE;
+    if (workspace_bytes < geo_align256((size_t)tiles * sizeof(unsigned int))) return MVS_E_WORKSPACE;
     hipStream_t st = mvs_stream(stream);
     hipError_t e = hipMemsetAsync(score_sum, 0, (size_t)V * V * sizeof(long long), st);
     if (e != hipSuccess) return (int)e;

@@ -183,17 +183,9 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
     return path
 
 
-def _gpu_ready():
-    """None when the HIP library loads and a GPU is visible, else the reason."""
-    try:
-        import torch
-        from . import _lib
-        _lib.load()
-    except Exception as e:                     # library missing or not loadable
-        return str(e)
-    if not torch.cuda.is_available():
-        return "no GPU is visible to this process"
-    return None
+def _gpu_ready():                              # the old private name of _lib.gpu_ready, kept for its callers
+    from ._lib import gpu_ready
+    return gpu_ready()
 
 
 def main(argv=None):

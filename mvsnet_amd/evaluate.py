@@ -209,17 +209,6 @@ def inlier_median(d, max_dist):
 
 # ------------------------------------------------------------------------------------------------ device side
 
-def _device(device):
-    import torch
-    from . import _lib
-    if not torch.cuda.is_available():
-        raise _lib.MvsnetHipError("point-cloud evaluation runs on the GPU (HIP); no GPU is visible to this process")
-    dev = torch.device(device) if device is not None else torch.device("cuda")
-    if dev.type != "cuda":
-        raise ValueError("point-cloud evaluation runs on a GPU device, got %s" % dev)
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def _points(x, name, dev):
     """numpy array or tensor (n,3) -> contiguous float32 tensor on dev; ValueError for other shapes or non-finite values."""
     import torch
@@ -280,12 +269,13 @@ def _voxel(t, s, name):
 def preprocess(pred, gt, *, transform=None, crop=None, voxel_pred=0.0, voxel_gt=0.0, device=None):
     """§ Preprocessing of the module docstring on the device -> (pred, gt) float32 (n,3) tensors, ValueError when empty."""
     import torch
+    from . import _lib
     T = check_transform(transform) if transform is not None else None
     box = check_crop(crop) if crop is not None else None
     for name, v in (("voxel_pred", voxel_pred), ("voxel_gt", voxel_gt)):
         if not (float(v) >= 0 and math.isfinite(float(v))):
             raise ValueError("%s must be >= 0, got %r" % (name, v))
-    dev = _device(device)
+    dev = _lib.device(device, "point-cloud evaluation")
     with torch.cuda.device(dev):
         p, g = _points(pred, "pred", dev), _points(gt, "gt", dev)
         if T is not None:
@@ -347,7 +337,7 @@ class NearestPlan:
     def __init__(self, query, target, max_dist, *, cell=None, device=None):
         import torch
         from . import _lib
-        self.dev = _device(device)
+        self.dev = _lib.device(device, "point-cloud evaluation")
         self.max_dist = float(max_dist)
         if not (self.max_dist > 0 and math.isfinite(self.max_dist)):
             raise ValueError("max_dist must be positive and finite, got %r" % max_dist)
@@ -511,8 +501,8 @@ def main(argv=None):
             raise SystemExit("mvsnet_amd.evaluate: %s" % e)
     elif a.align_stages or a.align_with_scale:
         raise SystemExit("mvsnet_amd.evaluate: --align_stages / --align_with_scale need --align icp")
-    from .depthfusion import _gpu_ready
-    why = _gpu_ready()
+    from ._lib import gpu_ready
+    why = gpu_ready()
     if why is not None:
         raise SystemExit("mvsnet_amd.evaluate needs a GPU and the HIP library: %s" % why)
     thresholds = _floats(a.thresholds, what="--thresholds")

@@ -202,26 +202,16 @@ def _check_views(depths, probs, cams, images):
 
 # ------------------------------------------------------------------------------------------------ device side
 
-def _device(device):
-    import torch
-    from . import _lib
-    dev = torch.device(device) if device is not None else torch.device("cuda")
-    if dev.type != "cuda":
-        raise ValueError("TSDF fusion runs on a GPU device, got %s" % dev)
-    if not torch.cuda.is_available():
-        raise _lib.MvsnetHipError("TSDF fusion runs on the GPU (HIP); no GPU is visible to this process")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 class TsdfVolume:
     """A volume on the device.  ``integrate`` may be called repeatedly (a session can be fed in groups of views) and only
     enqueues on torch's current stream; ``extract`` synchronises once, to size its outputs."""
 
     def __init__(self, origin, voxel, dims, trunc, colour=False, device=None):
         import torch
+        from . import _lib
         self.origin, self.voxel, self.dims, self.trunc = check_volume(origin, voxel, dims, trunc)      # before any GPU work
         self.colour = bool(colour)
-        self.dev = _device(device)
+        self.dev = _lib.device(device, "TSDF fusion")
         nx, ny, nz = self.dims
         self._origin_c = (ctypes.c_float * 3)(*[float(v) for v in self.origin])
         with torch.cuda.device(self.dev):
@@ -473,8 +463,8 @@ def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", **options):
 def main(argv=None):
     a = parse_args(argv)
     out = prepare_output(a)
-    from .depthfusion import _gpu_ready
-    why = _gpu_ready()
+    from ._lib import gpu_ready
+    why = gpu_ready()
     if why is not None:
         raise SystemExit("mvsnet_amd.mesh needs a GPU and the HIP library: %s" % why)
     try:

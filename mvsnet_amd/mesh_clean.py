@@ -83,17 +83,6 @@ def _shapes(vertices, colours, faces):
 
 # ------------------------------------------------------------------------------------------------ device side
 
-def _device(device):
-    import torch
-    from . import _lib
-    dev = torch.device(device) if device is not None else torch.device("cuda")
-    if dev.type != "cuda":
-        raise ValueError("mesh cleaning runs on a GPU device, got %s" % dev)
-    if not torch.cuda.is_available():
-        raise _lib.MvsnetHipError("mesh cleaning runs on the GPU (HIP); no GPU is visible to this process")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def _tensor(x, name, dtype, np_dtype, dev):
     import torch
     if x is None:
@@ -108,13 +97,14 @@ def _tensor(x, name, dtype, np_dtype, dev):
 def _inputs(vertices, colours, faces, device):
     """-> (device, vertices, colours or None, faces) as contiguous tensors on the device; ValueError for wrong shapes."""
     import torch
+    from . import _lib
     for x in (vertices, faces, colours):
         if x is not None and not hasattr(x, "shape"):
             raise ValueError("vertices, colours and faces must be arrays or tensors")
     _shapes(vertices, colours, faces)                                          # before any GPU work
     if device is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
         device = vertices.device
-    dev = _device(device)
+    dev = _lib.device(device, "mesh cleaning")
     return (dev, _tensor(vertices, "vertices", torch.float32, np.float32, dev), _tensor(colours, "colours", torch.uint8, np.uint8, dev),
             _tensor(faces, "faces", torch.int32, np.int32, dev))
 
@@ -299,9 +289,9 @@ def prepare_output(a):
 def main(argv=None):
     a = parse_args(argv)
     out = prepare_output(a)
-    from .depthfusion import _gpu_ready
+    from ._lib import gpu_ready
     from .mesh import read_mesh_ply, write_mesh_ply
-    why = _gpu_ready()
+    why = gpu_ready()
     if why is not None:
         raise SystemExit("mvsnet_amd.mesh_clean needs a GPU and the HIP library: %s" % why)
     try:

@@ -157,7 +157,7 @@ class RegistrationPlan:
             max_corr_dist, max_iterations, fitness_tol, rmse_tol)
         self.init = check_transform(init) if init is not None else np.eye(4)
         self.with_scale = bool(with_scale)
-        self.dev = E._device(device)
+        self.dev = _lib.device(device, "point-cloud evaluation")
         with torch.cuda.device(self.dev):
             self.source, self.target = E._points(source, "source", self.dev), E._points(target, "target", self.dev)
             ns, nt = self.source.shape[0], self.target.shape[0]
@@ -256,11 +256,12 @@ def register_point_clouds(source, target, *, stages, init=None, with_scale=False
     """Multi-stage ICP (module docstring) -> {"transform": 4x4 list, "stopped": the last stage's reason, "stages": [each
     stage's RegistrationPlan.run() result plus "voxel", "max_corr_dist", "source_points", "target_points"]}."""
     import torch
+    from . import _lib
     from . import evaluate as E
     stages = check_stages(stages)
     T = check_transform(init) if init is not None else np.eye(4)
     box = check_crop(crop) if crop is not None else None
-    dev = E._device(device)
+    dev = _lib.device(device, "point-cloud evaluation")
     with torch.cuda.device(dev):
         src, tgt = E._points(source, "source", dev), E._points(target, "target", dev)
         if box is not None:
@@ -302,8 +303,8 @@ def main(argv=None):
         stages = parse_stages(a.stages)
     except ValueError as e:
         raise SystemExit("mvsnet_amd.register: %s" % e)
-    from .depthfusion import _gpu_ready
-    why = _gpu_ready()
+    from ._lib import gpu_ready
+    why = gpu_ready()
     if why is not None:
         raise SystemExit("mvsnet_amd.register needs a GPU and the HIP library: %s" % why)
     crop = _floats(a.crop, 6, "--crop") if a.crop else None

@@ -163,17 +163,6 @@ def size_groups(views):
 
 # ------------------------------------------------------------------------------------------------ device side
 
-def _device(device):
-    import torch
-    from . import _lib
-    dev = torch.device(device) if device is not None else torch.device("cuda")
-    if dev.type != "cuda":
-        raise ValueError("point-cloud rendering runs on a GPU device, got %s" % dev)
-    if not torch.cuda.is_available():
-        raise _lib.MvsnetHipError("point-cloud rendering runs on the GPU (HIP); no GPU is visible to this process")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 class RenderPlan:
     """Points and projection tables on the device, outputs and workspace allocated once (the constructor synchronises when it
     computes the processing order).  ``enqueue()`` only launches on torch's current stream (no allocation, no
@@ -206,7 +195,7 @@ class RenderPlan:
             raise ValueError("points must be (n,3) with n >= 1, got %s" % (tuple(shape),))
         if shape[0] > 2 ** 31 - 1:
             raise ValueError("%d points are beyond the kernel's int32 indices" % shape[0])
-        self.dev = _device(device)
+        self.dev = _lib.device(device, "point-cloud rendering")
         self.n = int(shape[0])
         lib = _lib.load()
         wsb = lib.mvs_render_workspace_bytes(self.V, self.H, self.W, 1 if self.occlusion else 0)
@@ -344,17 +333,18 @@ def prepare_output(a):
 def main(argv=None):
     a = parse_args(argv)
     out_dir = prepare_output(a)
-    from .depthfusion import _gpu_ready
-    why = _gpu_ready()
+    from ._lib import gpu_ready
+    why = gpu_ready()
     if why is not None:
         raise SystemExit("mvsnet_amd.render needs a GPU and the HIP library: %s" % why)
     import torch
+    from . import _lib
     from . import evaluate as E
     from .preprocess import write_pfm
     try:
         views = session_views(a.session) if a.session is not None else dense_folder_views(a.dense_folder)
         pts, _ = E.read_ply_points(a.cloud)
-        dev = _device(None)
+        dev = _lib.device(None, "point-cloud rendering")
         with torch.cuda.device(dev):
             t = E._points(pts, "cloud", dev)
             if a.cloud_scale != 1.0:

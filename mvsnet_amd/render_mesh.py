@@ -65,7 +65,7 @@ import sys
 
 import numpy as np
 
-from .render import _device, dense_folder_views, projection_tables, session_views, size_groups, write_depth_png
+from .render import dense_folder_views, projection_tables, session_views, size_groups, write_depth_png
 
 MAX_AXIS = 1 << 20              # csrc/raster.hip RS_MAX_AXIS
 MAX_CHANNELS = 8                # RS_MAX_CHANNELS
@@ -135,7 +135,7 @@ class RasterPlan:
         self.V = int(cams.shape[0])
         vertices, self.M = _array(vertices, np.float32, 3, "vertices")
         faces, self.F = _array(faces, np.int32, 3, "faces")
-        self.dev = _device(device)
+        self.dev = _lib.device(device, "point-cloud rendering")
         lib = _lib.load()
         wsb = lib.mvs_raster_workspace_bytes(self.V, self.H, self.W, self.queue_capacity)
         if wsb == 0:
@@ -305,11 +305,12 @@ def write_view(a, stem, depth, index=None, color=None):
 def main(argv=None):
     a = parse_args(argv)
     out_dir = prepare_output(a)
-    from .depthfusion import _gpu_ready
-    why = _gpu_ready()
+    from ._lib import gpu_ready
+    why = gpu_ready()
     if why is not None:
         raise SystemExit("mvsnet_amd.render_mesh needs a GPU and the HIP library: %s" % why)
     import torch
+    from . import _lib
     from . import evaluate as E
     from .mesh import read_mesh_ply
     try:
@@ -317,7 +318,7 @@ def main(argv=None):
         verts, rgb, faces = read_mesh_ply(a.mesh)
         if len(verts) == 0 or len(faces) == 0:
             raise ValueError("%s holds no faces" % a.mesh)
-        dev = _device(None)
+        dev = _lib.device(None, "point-cloud rendering")
         with torch.cuda.device(dev):
             t = E._points(verts, "mesh", dev)
             if a.mesh_scale != 1.0:

@@ -333,16 +333,17 @@ def prepare_output(a):
 def main(argv=None):
     a = parse_args(argv)
     out = prepare_output(a)
-    from .depthfusion import _gpu_ready
-    why = _gpu_ready()
+    from ._lib import gpu_ready
+    why = gpu_ready()
     if why is not None:
         raise SystemExit("mvsnet_amd.select_views needs a GPU and the HIP library: %s" % why)
     import torch
+    from . import _lib
     from . import evaluate as E
     try:
         views = Rn.session_views(a.session) if a.session is not None else Rn.dense_folder_views(a.dense_folder)
         pts, _ = E.read_ply_points(a.cloud)
-        dev = Rn._device(None)
+        dev = _lib.device(None, "point-cloud rendering")
         with torch.cuda.device(dev):
             t = E._points(pts, "cloud", dev)
             if a.cloud_scale != 1.0:

@@ -122,6 +122,30 @@ def test_device_explicit_source_lists():
         assert not (got[2] == 3).any()                                 # view 3 has no sources
 
 
+# V x H x W with V*H*W = one pixel; one below, exactly and one above a compaction block of 1024 pixels; and 263 blocks, past the
+# 256 block counts that the single-workgroup scan takes per round
+COMPACTION_SHAPES = {1: (1, 1, 1), 1023: (3, 11, 31), 1024: (2, 16, 32), 1025: (5, 5, 41), 268800: (5, 240, 224)}
+
+
+@pytest.mark.parametrize("pixels", sorted(COMPACTION_SHAPES))
+def test_compaction_at_block_boundaries(pixels):
+    """With num_consistent = 0 a pixel is kept exactly when it is valid, whatever its sources say, so the probabilities place
+    the survivors: the first and the last pixel, about 30 % of the rest, and (263 blocks) none in blocks 1, 100 and 261."""
+    V, H, W = COMPACTION_SHAPES[pixels]
+    s = FR.make_scene(kind="plane", V=V, H=H, W=W, layout="line", f=64.0, seed=pixels)
+    keep = np.random.RandomState(pixels).rand(pixels) < 0.3
+    keep[0] = keep[-1] = True
+    blocks = -(-pixels // 1024)
+    for b in ((1, 100, blocks - 2) if blocks > 3 else ()):
+        keep[b * 1024:(b + 1) * 1024] = False
+    s["probs"] = np.where(keep, 1.0, 0.3).astype(np.float32).reshape(V, H, W)
+    ref = FR.reference_fusion(s["depths"], s["probs"], s["cams"], s["images"], num_consistent=0, dedupe=False)
+    assert np.array_equal(ref["keep"].reshape(-1), keep)
+    got = _run(s, num_consistent=0, dedupe=False)
+    assert np.array_equal(got[2].astype(np.int64) * H * W + got[3], np.nonzero(keep)[0])
+    _compare_exact_where_margin(s, ref, got, H, W)
+
+
 def test_reproducible_bytes(tmp_path):
     from mvsnet_amd import fusion as F
     s = _scene("sphere", V=6, H=64, W=80)

@@ -146,6 +146,29 @@ def test_preprocessing_on_device_matches_reference():
         E.evaluate_point_clouds(pred, gt, max_dist=md, crop=(1e3, 1e3, 1e3, 2e3, 2e3, 2e3))
 
 
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 256 * 1024 + 1])
+def test_voxel_compaction_at_block_boundaries(n):
+    """The compaction of mvs_voxel_select_f32 where its scans can go wrong: one point; one below, exactly and one above a
+    compaction block of 1024 points; and 257 blocks, the first count that takes the single-workgroup scan of the block
+    counts (256 per round) into a second round.  A survivor sits alone in voxel i of the x axis and every other point shares
+    point 0's voxel, so the keep flags are the pattern: the first and the last point, about 30 % of the rest, and (257 blocks)
+    none in blocks 1, 100 and 255."""
+    from mvsnet_amd import evaluate as E
+    keep = np.random.RandomState(n).rand(n) < 0.3
+    keep[0] = keep[-1] = True
+    blocks = -(-n // 1024)
+    for b in ((1, 100, blocks - 2) if blocks > 3 else ()):
+        keep[b * 1024:(b + 1) * 1024] = False
+    i = np.arange(n)
+    pts = np.zeros((n, 3), np.float32)
+    pts[:, 0] = np.where(keep, i + 0.5, 0.5)                                   # exact in float32 up to 2^18 + 1/2
+    pts[:, 1] = (i % 7) / 16.0                                                 # distinct points inside a voxel
+    want = R.voxel_first(pts, 1.0)
+    assert want.tobytes() == pts[keep].tobytes()
+    got, _ = E.preprocess(pts, pts[:1], voxel_pred=1.0)
+    assert got.cpu().numpy().tobytes() == want.tobytes()
+
+
 def test_reproducible_and_graph_replay():
     import torch
     from mvsnet_amd import evaluate as E
