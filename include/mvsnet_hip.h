@@ -35,6 +35,36 @@
  *     and affines are never modified.  A call refused with MVS_E_WORKSPACE has enqueued nothing and written nothing;
  *   - the result does not depend on what lies outside the inputs: SAME padding and out-of-image taps are zeros (or clamped
  *     taps) formed by the kernels, and no load leaves a tensor's extent.
+ *
+ * Memory contract of the geometry entry points (everything declared from mvs_fusion_workspace_bytes to the end of this header:
+ * fusion, point cloud, render, view selection, TSDF and surface nets, raster, mesh components; tests/test_gpu_arena_geometry.py
+ * runs each of them in the same arena and lists, piece by piece, what first writes every workspace word).  The five rules above
+ * hold for them as well, with these particulars:
+ *   - alignment: 16 bytes for every pointer is enough in every family, workspaces included (they are carved at 256-byte
+ *     multiples of their own start; the widest accesses are the 16-byte points and normals of the sorted copies and the normal
+ *     map, and 8-byte keys, masks, queue entries and sums).  No entry point checks alignment and none needs more;
+ *   - accumulators the caller clears before the first call, and which a later call continues: sum, count, rgb_sum and rgb_count
+ *     of mvs_tsdf_integrate_f32 (every node is read, added to and stored back), and the mask of mvs_view_visibility_f32 (bits are
+ *     ORed in; bits the call's views do not name are kept).  Nothing else has to be cleared by the caller;
+ *   - outputs that the call stores whatever they held (none of them is added to): count of mvs_fusion_f32 / mvs_fusion_normals_f32
+ *     and of mvs_voxel_select_f32, moments of mvs_icp_step_f32, out of mvs_dist_stats_f32 (2 + n_thresholds doubles), totals of
+ *     mvs_surface_nets_count_f32, score_sum and shared of mvs_view_scores_f32 (all V x V entries, zeros where a >= b), hist of
+ *     mvs_view_depth_hist_f32 (all V x (pass + 1) x 65536 bins), vertex_keep of mvs_mesh_compact_mark_i32, counts and boxes of
+ *     mvs_mesh_components_measure_f32, depth and index of the two z-buffer calls;
+ *   - capacity outputs are written up to what is produced and not a byte further: xyz, rgb, normals, view_index and pixel_index
+ *     of the fusion calls and out of mvs_voxel_select_f32 hold *count entries and are untouched from entry *count on; vertices,
+ *     colours and faces of mvs_surface_nets_write_f32 are untouched beyond the totals of the count call when M or F is larger
+ *     (and not written at all when an axis has one node); out_vertices, out_colours and out_faces of mvs_mesh_compact_write_f32
+ *     are untouched beyond the last rank when M_out or F_out is larger;
+ *   - workspaces hold anything on entry and every word a call reads was written earlier in that call (counters, cell starts,
+ *     used / keep flags, the z-buffer keys, the raster queue's counter and the 64 status words are cleared by the call), so
+ *     one workspace serves calls of changing shape back to back.  Four workspaces carry state to a LATER call, which reads
+ *     them as the earlier call left them and needs the same sizes and grid: mvs_nn_f32 -> mvs_nn_query_f32 and
+ *     mvs_nn_target_build_f32 -> mvs_icp_step_f32 (both readers take the workspace as const and do not write it),
+ *     mvs_mesh_components_label_i32 -> mvs_mesh_components_measure_f32 (which stores status word 2), and
+ *     mvs_surface_nets_count_f32 -> the caller's two scans -> mvs_surface_nets_write_f32 (which only reads it);
+ *   - a call that returns MVS_E_BADARG, MVS_E_SHAPE or MVS_E_WORKSPACE has enqueued nothing: outputs, accumulators and the
+ *     workspace hold what they held.  mvs_*_workspace_bytes() is exact: one byte less is refused.
  */
 #ifndef MVSNET_HIP_H_
 #define MVSNET_HIP_H_
@@ -632,8 +662,8 @@ int mvs_fusion_f32(const float* depth, const float* prob, int V, int H, int W, c
  *                 pair is consistent only when n_r . n_s > normal_cos_threshold (must be < 1)
  *     normals     (V*H*W,3) float32, capacity as xyz: per point the normalised sum of its reference pixel's normal and its
  *                 consistent sources' normals (fixed slice order: bitwise reproducible), (0,0,0) when that sum is zero
- *     workspace   mvs_fusion_normals_workspace_bytes(V, H, W, max_sources, dedupe) bytes, 16-byte aligned (it holds the
- *                 normal maps as 16 bytes per pixel)
+ *     workspace   mvs_fusion_normals_workspace_bytes(V, H, W, max_sources, dedupe) bytes (it also holds the normal maps, 16
+ *                 bytes per pixel)
  * Error codes as mvs_fusion_f32. */
 int mvs_depth_normals_f32(const float* depth, const float* prob, int V, int H, int W, const float* tables, float prob_threshold,
                           float jump_threshold, float* normals, void* stream);

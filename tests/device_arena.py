@@ -92,6 +92,19 @@ class Arena:
         """A workspace of exactly n bytes (uint8), poisoned."""
         return self.take((int(n),), torch.uint8, name=name or "workspace%d" % len(self.regions), align=align)
 
+    def freeze(self, view):
+        """From now on the region handed out as `view` is read-only: its bytes as they stand (after the work enqueued so far)
+        are snapshotted, and check() asserts that they are still there.  For state that one call produces and later calls
+        take as const, such as a workspace that carries a grid.  Freezing again takes a new snapshot."""
+        if self.buf.is_cuda:
+            torch.cuda.synchronize(self.buf.device)
+        begin = view.data_ptr() - self.base
+        for r in self.regions:
+            if r.begin == begin and r.end - r.begin == view.numel() * view.element_size():
+                r.saved = self.buf[r.begin:r.end].clone()
+                return view
+        raise ValueError("freeze() takes a whole region handed out by take() or take_bytes()")
+
     # -- checking -----------------------------------------------------------------------------------------------------------
     def _gaps(self):
         """(begin, end, region before or None, region after or None) of every stretch of guard bytes."""

@@ -131,3 +131,44 @@ def test_a_changed_read_only_region_is_named(pattern):
         a.check()
     with pytest.raises(ValueError):
         a.take((2,), torch.float32, readonly=True)
+
+
+@pytest.mark.parametrize("pattern", PATTERNS)
+def test_a_frozen_region_is_held_to_the_bytes_it_had_when_frozen(pattern):
+    a = Arena(10 * GUARD, pattern)
+    a.take((6,), torch.float32, name="before")
+    ws = a.take_bytes(1001, name="grid workspace")
+    out = a.take((5,), torch.int32, name="out")
+    ws[:500] = 3                                                                   # the producing call writes it ...
+    a.check()
+    assert a.freeze(ws) is ws                                                      # ... and from here on it is const
+    a.check()
+    out.fill_(4)                                                                   # other regions may still change
+    a.check()
+    ws[17] = 3                                                                     # the same byte again: fine
+    a.check()
+    ws[700] = 0x11                                                                 # a byte that still held the pattern when frozen
+    with pytest.raises(ArenaError, match=r"read-only region 'grid workspace' changed: bytes 700 \.\. 700 of 1001"):
+        a.check()
+    ws[700] = pattern
+    ws[3] = 9                                                                      # a byte the producer wrote
+    with pytest.raises(ArenaError, match=r"read-only region 'grid workspace' changed: bytes 3 \.\. 3 of 1001"):
+        a.check()
+    # a second freeze accepts the region as it now stands
+    a.freeze(ws)
+    a.check()
+    assert not a.is_pattern(ws) and a.is_pattern(a.take((2,), torch.float32))
+
+
+def test_freeze_takes_whole_regions_only():
+    a = Arena(8 * GUARD, 0xFF)
+    x = a.take((8,), torch.float32, name="x")
+    with pytest.raises(ValueError):
+        a.freeze(x[2:])                                                            # a part of a region
+    with pytest.raises(ValueError):
+        a.freeze(x[:4])
+    with pytest.raises(ValueError):
+        a.freeze(torch.zeros(8))                                                   # not the arena's memory
+    ro = a.take((3,), torch.float32, data=np.ones(3, np.float32), readonly=True, name="ro")
+    a.freeze(ro)                                                                   # already read-only: a new snapshot of the same bytes
+    a.check()

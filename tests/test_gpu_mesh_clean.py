@@ -73,21 +73,7 @@ def test_the_noisy_plane_loses_its_fragments():
 
 # ------------------------------------------------------------------------------------------------ built meshes
 
-@functools.lru_cache(maxsize=None)
-def _strip(n_faces, seed, cuts=0):
-    """A strip of n_faces triangles (i, i+1, i+2) on n_faces + 2 vertices with vertex numbering and face order permuted; with
-    cuts, every face whose index is a multiple of n_faces // cuts is left out twice over (it and its successor), so the
-    strip falls into pieces."""
-    rs = np.random.RandomState(seed)
-    i = np.arange(n_faces)
-    if cuts:
-        step = n_faces // cuts
-        i = i[(i % step > 1) | (i < 2)]
-    number = rs.permutation(n_faces + 2)
-    faces = number[np.stack([i, i + 1, i + 2], 1)][rs.permutation(len(i))].astype(np.int32)
-    vertices = np.zeros((n_faces + 2, 3), np.float32)
-    vertices[number] = np.stack([np.arange(n_faces + 2) * 0.5, np.arange(n_faces + 2) % 2, np.zeros(n_faces + 2)], 1)
-    return vertices, faces
+_strip, _grid = R.strip, R.grid            # the built meshes live beside the reference: test_gpu_arena_geometry.py uses them too
 
 
 @pytest.mark.parametrize("seed", [0, 1])
@@ -135,20 +121,6 @@ def test_one_hot_word():
     same = np.tile(np.array([[7, 3, 5]], np.int32), (4096, 1))                 # 4 096 copies of one face
     got = _check(v, None, same, min_faces=4096)
     assert got[3]["largest"][0][:2] == [3, 4096] and got[3]["vertices_out"] == 3 and got[3]["unreferenced"] == 8997
-
-
-@functools.lru_cache(maxsize=None)
-def _grid(n, gap=0):
-    """n x n quads on (n+1)^2 vertices, two triangles each; with gap, every gap-th row of quads is left out."""
-    j, i = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
-    if gap:
-        keep = (j % gap) != gap - 1
-        j, i = j[keep], i[keep]
-    a = (j * (n + 1) + i).reshape(-1)
-    faces = np.stack([np.stack([a, a + 1, a + n + 2], 1), np.stack([a, a + n + 2, a + n + 1], 1)], 1).reshape(-1, 3).astype(np.int32)
-    y, x = np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing="ij")
-    vertices = np.stack([x.reshape(-1) * 0.25, y.reshape(-1) * 0.25, np.sin(x.reshape(-1) * 0.1)], 1).astype(np.float32)
-    return vertices, faces
 
 
 def test_a_grid_of_quads():
