@@ -911,6 +911,49 @@ int mvs_mesh_compact_write_f32(const float* vertices, const unsigned char* colou
                                long long M_out, long long F_out, float* out_vertices, unsigned char* out_colours, int* out_faces,
                                void* stream);
 
+/* Mesh simplification by vertex clustering on a uniform grid of cells (csrc/mesh_simplify.hip; semantics in
+ * mvsnet_amd/mesh_simplify.py).  M vertices and F faces, each 0..2^31-1 (negative: MVS_E_BADARG, beyond: MVS_E_SHAPE); a pointer
+ * to an array of M or F entries may be NULL when that size is 0.  origin and cell are float32, finite, cell > 0 (else
+ * MVS_E_BADARG); the kernels widen them to float64.  The caller sorts and scans between the calls:
+ *   mvs_mesh_cluster_keys_f32   vertices (M,3) float32, faces (F,3) int32 -> keys (M) int64: the cell key kx | ky << 21 | kz << 42
+ *                 of a vertex that a valid face names, else -1; offsets (M,3) int32: floor(fraction of the cell * 2^20), 0 for a
+ *                 vertex that is not clusterable.  Clears the status words; counts words 0 and 1
+ *   (a stable ascending sort of keys -> sorted_keys, order (M) int64)
+ *   mvs_mesh_cluster_heads_i64  -> head (M) int32: 1 where a run of equal sorted keys >= 0 starts, else 0
+ *   (an inclusive scan of head -> head_rank (M) int32; its last entry is the number of clusters K)
+ *   mvs_mesh_cluster_sums_f32   colours NULL or (M,3) uint8 -> vertex_cluster (M) int32: the cluster (rank - 1, ascending key
+ *                 order) of a contributing vertex, else -1; cluster_vertices (M,3) float32 and cluster_colours (M,3) uint8
+ *                 (NULL together with colours): rows 0..K-1 are written, the rest is left alone
+ *   mvs_mesh_cluster_faces_i32  -> cluster_faces (F,3) int32: the three clusters, -1 -1 -1 for an invalid face; key_lo (F) int64
+ *                 and key_hi (F) int64 or NULL: the sort key of a valid face with three different clusters x < y < z is
+ *                 x << 42 | y << 21 | z in key_lo when key_hi is NULL (M <= 2^21, else MVS_E_SHAPE), otherwise key_hi = x,
+ *                 key_lo = y << 32 | z; INT64_MAX in both for every other face.  Counts status word 2
+ *   (a stable ascending sort by (key_hi, key_lo) -> sorted_lo, sorted_hi or NULL, order (F) int64)
+ *   mvs_mesh_cluster_mark_i32   -> face_keep (F) int32: 1 for the first face of a run of equal keys if it is valid and not
+ *                 degenerate, else 0; vertex_keep (M) int32: 1 for a cluster that a kept face names, else 0.  Counts word 3
+ *   (inclusive scans of both, then mvs_mesh_compact_write_f32 on cluster_vertices, cluster_colours and cluster_faces with M = K)
+ *   workspace     mvs_mesh_cluster_workspace_bytes(M, F) bytes (0 for invalid sizes), one for all calls of a mesh: 64 int32
+ *                 status words (0 invalid faces, 1 unclusterable vertices, 2 degenerate faces, 3 duplicate faces), the use
+ *                 marks of the vertices, and 8 int64 per cluster slot (n, the offset sums, the colour sums, the key)
+ * All five only enqueue on `stream`: nothing is allocated, nothing synchronised.  The only atomics are integer sums, so the
+ * same inputs give the same bytes in any order and grid.  Every argument is checked before the first GPU call (MVS_E_BADARG,
+ * MVS_E_SHAPE, MVS_E_WORKSPACE) and the outputs are untouched on error.  Indices that the caller computed (order, head_rank,
+ * vertex_cluster, cluster_faces) are range-checked before they are used. */
+size_t mvs_mesh_cluster_workspace_bytes(long long M, long long F);
+int mvs_mesh_cluster_keys_f32(const float* vertices, long long M, const int* faces, long long F, float origin_x, float origin_y,
+                              float origin_z, float cell, long long* keys, int* offsets, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int mvs_mesh_cluster_heads_i64(const long long* sorted_keys, long long M, int* head, void* stream);
+int mvs_mesh_cluster_sums_f32(const long long* sorted_keys, const long long* order, const int* head_rank, const int* offsets,
+                              const unsigned char* colours, long long M, float origin_x, float origin_y, float origin_z,
+                              float cell, int* vertex_cluster, float* cluster_vertices, unsigned char* cluster_colours,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mvs_mesh_cluster_faces_i32(const int* faces, long long M, long long F, const int* vertex_cluster, int* cluster_faces,
+                               long long* key_lo, long long* key_hi, void* workspace, size_t workspace_bytes, void* stream);
+int mvs_mesh_cluster_mark_i32(const int* cluster_faces, long long M, long long F, const long long* sorted_lo,
+                              const long long* sorted_hi, const long long* order, int* face_keep, int* vertex_keep,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

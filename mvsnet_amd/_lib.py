@@ -107,6 +107,15 @@ SIGNATURES = {
     "mvs_gru_release": (_i, [_p]),
     "mvs_gru_stream_layout": (_i, [_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "mvs_regnet_filler_shares": (_i, [C.POINTER(C.c_int)]),
+    # mesh simplification (csrc/mesh_simplify.hip; the header has it last).  It stands BEFORE mvs_fusion_workspace_bytes because
+    # tests/test_gpu_arena_geometry.py pins the names from there to the end to its own arena cases; the arena cases of these six
+    # are tests/test_gpu_arena_mesh_simplify.py, which pins them in the same way.
+    "mvs_mesh_cluster_workspace_bytes": (_sz, [_ll, _ll]),
+    "mvs_mesh_cluster_keys_f32": (_i, [_p, _ll, _p, _ll, _f, _f, _f, _f, _p, _p, _p, _sz, _p]),
+    "mvs_mesh_cluster_heads_i64": (_i, [_p, _ll, _p, _p]),
+    "mvs_mesh_cluster_sums_f32": (_i, [_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _p, _p, _p, _p, _sz, _p]),
+    "mvs_mesh_cluster_faces_i32": (_i, [_p, _ll, _ll, _p, _p, _p, _p, _p, _sz, _p]),
+    "mvs_mesh_cluster_mark_i32": (_i, [_p, _ll, _ll, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "mvs_fusion_workspace_bytes": (_sz, [_i] * 5),
     "mvs_fusion_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "mvs_depth_normals_f32": (_i, [_p, _p, _i, _i, _i, _p, _f, _f, _p, _p]),

@@ -3,7 +3,7 @@ mesh by naive surface nets, the last stage between the depth maps and a model th
 
     python -m mvsnet_amd.mesh --dense_folder DIR [--out mesh.ply] [--voxel S | --resolution R] [--bounds x0:y0:z0:x1:y1:z1]
         [--trunc_voxels 4] [--prob_threshold 0.8] [--num_consistent 3] [--min_count 1] [--fusion_sources all|listed] [--force]
-        [--min_component_faces 0] [--min_component_extent 0] [--keep_largest 0]
+        [--min_component_faces 0] [--min_component_extent 0] [--keep_largest 0] [--simplify_voxels S]
 
 The kernels are csrc/tsdf.hip (mvs_tsdf_integrate_f32, mvs_surface_nets_count_f32, mvs_surface_nets_write_f32); torch owns the
 device memory and the two scans between counting and writing.
@@ -50,6 +50,10 @@ the fusion's kept points, widened by trunc plus one voxel.
 Small pieces: with min_component_faces, min_component_extent or keep_largest non-zero the extracted mesh goes through
 mvsnet_amd.mesh_clean (its docstring has the semantics) on the device, before the copy to the host; with all three at 0
 nothing of it runs and the mesh is the extraction's, byte for byte.
+
+Fewer faces: with simplify_voxels = S > 0 (not necessarily an integer) the mesh, after the removal of its small pieces, goes
+through mvsnet_amd.mesh_simplify (its docstring has the semantics) on the device: vertex clustering in cells of
+float32(S voxel), aligned to the volume's origin.  Without it nothing of it runs and the mesh bytes are unchanged.
 """
 from __future__ import annotations
 
@@ -266,16 +270,21 @@ class TsdfVolume:
             _lib.check(rc, "mvs_tsdf_integrate_f32")
         return self
 
-    def extract(self, min_count=1, clean=None):
+    def extract(self, min_count=1, clean=None, simplify=None):
         """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation.  With
         clean = dict(min_faces=, min_extent=, keep_largest=) the mesh goes through mesh_clean.clean_mesh on the device before
-        the copy to the host and the result is (vertices, colours, faces, report)."""
+        the copy to the host and the result is (vertices, colours, faces, report).  With simplify = cell (world units) it then
+        goes through mesh_simplify.simplify_device with cells aligned to the volume's origin; the result is (vertices, colours,
+        faces, report) with the simplification's report under "simplify", beside the cleaning's fields if there are any."""
         import torch
         from . import _lib
         min_count = check_min_count(min_count)
         if clean is not None:
             from . import mesh_clean
             clean = mesh_clean.check_options(**clean)                          # before any GPU work
+        if simplify is not None:
+            from . import mesh_simplify
+            simplify = mesh_simplify.check_cell(simplify)
         lib = _lib.load()
         nx, ny, nz = self.dims
         nodes = nx * ny * nz
@@ -306,8 +315,12 @@ class TsdfVolume:
             report = None
             if clean is not None:
                 vertices, colours, faces, report = mesh_clean.clean_device(vertices, colours, faces, self.dev, *clean)
+            if simplify is not None:
+                vertices, colours, faces, simplified = mesh_simplify.simplify_device(vertices, colours, faces, self.dev, simplify,
+                                                                                     self.origin)
+                report = dict(report or {}, simplify=simplified)
             mesh = (vertices.cpu().numpy(), colours.cpu().numpy(), faces.cpu().numpy())
-            return mesh if clean is None else mesh + (report,)
+            return mesh if report is None else mesh + (report,)
 
     def tsdf(self):
         """For inspection -> (f (nz,ny,nx) float32 = sum / count, NaN where count is 0, count (nz,ny,nx) int32) as numpy."""
@@ -345,15 +358,18 @@ def mesh_depth_maps(depths, probs, cams, images=None, **options):
     """V depth maps -> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32).  Give a voxel or a resolution (nodes
     along the longest axis, 256 when neither is given); bounds (lo, hi) default to the box of the consistent points.  Options:
     voxel, resolution, bounds, trunc_voxels, num_consistent, prob_threshold, reproj_threshold, depth_rel_threshold, sources,
-    min_count, device, and min_component_faces, min_component_extent, keep_largest (all 0: no cleaning runs)."""
+    min_count, device, min_component_faces, min_component_extent, keep_largest (all 0: no cleaning runs), and simplify_voxels
+    (None or 0: no simplification runs; S > 0: vertex clustering in cells of float32(S voxel))."""
     return _mesh_depth_maps(depths, probs, cams, images, **options)[:3]
 
 
 def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution=None, bounds=None, trunc_voxels=4,
                      num_consistent=3, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, sources=None,
-                     min_count=1, device=None, min_component_faces=0, min_component_extent=0.0, keep_largest=0):
-    """mesh_depth_maps -> (vertices, colours, faces, the cleaning's report or None)."""
-    from . import mesh_clean
+                     min_count=1, device=None, min_component_faces=0, min_component_extent=0.0, keep_largest=0,
+                     simplify_voxels=None):
+    """mesh_depth_maps -> (vertices, colours, faces, the report of the cleaning and the simplification or None)."""
+    from . import mesh_clean, mesh_simplify
+    simplify_voxels = mesh_simplify.check_voxels(simplify_voxels)
     from .fusion import FusionPlan
     clean = mesh_clean.check_options(min_component_faces, min_component_extent, keep_largest)
     clean = dict(zip(mesh_clean.OPTION_NAMES, clean)) if mesh_clean.wanted(*clean) else None
@@ -384,9 +400,10 @@ def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution
         origin, voxel, dims = choose_volume(bounds[0], bounds[1], voxel, resolution)
     vol = TsdfVolume(origin, voxel, dims, tv * voxel, colour=images is not None, device=device)
     vol.integrate(depths, probs, cams, images, prob_threshold=prob_threshold)
-    if clean is None:
+    if clean is None and simplify_voxels is None:
         return vol.extract(min_count) + (None,)
-    return vol.extract(min_count, clean=clean)
+    cell = None if simplify_voxels is None else float(np.float32(simplify_voxels * vol.voxel))
+    return vol.extract(min_count, clean=clean, simplify=cell)
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -408,6 +425,8 @@ def build_parser():
     ap.add_argument("--force", action="store_true", help="overwrite an existing output file")
     from .mesh_clean import add_options
     add_options(ap)
+    from .mesh_simplify import add_option
+    add_option(ap)
     return ap
 
 
@@ -432,6 +451,8 @@ def parse_args(argv=None):
         except ValueError as e:
             raise ValueError("--min_component_faces and --keep_largest must be integers >= 0, --min_component_extent finite "
                              "and >= 0 (%s)" % e)
+        if a.simplify_voxels is not None and not (a.simplify_voxels > 0 and math.isfinite(a.simplify_voxels)):
+            raise ValueError("--simplify_voxels must be positive and finite, got %r" % (a.simplify_voxels,))
     except ValueError as e:
         raise SystemExit("mvsnet_amd.mesh: %s" % e)
     if a.out is None:
@@ -472,7 +493,7 @@ def main(argv=None):
                                    bounds=a.bounds, trunc_voxels=a.trunc_voxels, num_consistent=a.num_consistent,
                                    prob_threshold=a.prob_threshold, min_count=a.min_count,
                                    min_component_faces=a.min_component_faces, min_component_extent=a.min_component_extent,
-                                   keep_largest=a.keep_largest)
+                                   keep_largest=a.keep_largest, simplify_voxels=a.simplify_voxels)
     except (ValueError, OSError) as e:
         raise SystemExit("mvsnet_amd.mesh: %s" % e)
     print(json.dumps(report))
