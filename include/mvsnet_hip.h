@@ -123,7 +123,8 @@ int mvs_get_conv_impl(void);
 #define MVS_HOOK_PAIR_PLANES          14  /* even, >= 2: planes per workgroup of the fused 3dconv0_1 + 1_0 launch, in whole chunks (no SPAN); 0 (default) = the launcher's choice.  BatchNorm sums arrive in another order: last bits */
 #define MVS_HOOK_S1_PLANES            15  /* >= 1: planes per workgroup of the stride-1 plane-march kernels (conv3d_s1_kernel and the unfused 32 -> 8 kernel); 0 (default) = the launcher's choice.  Last bits, as above */
 #define MVS_HOOK_SPAN_FORCE           16  /* G << 8 | M (G = 1..8 tiles per group, M = G..16 ranges): the fused 3dconv0_1 + 1_0 launch takes the SPAN schedule with that pair at any size, if the launcher's other rules allow it (whole chunks if not); 0 (default) = the launcher's choice.  Last bits, as above */
-#define MVS_HOOK_COUNT                17
+#define MVS_HOOK_PAIR_DIRECT          17  /* 1: the fused 3dconv0_1 + 1_0 launch takes the direct kernel (conv3d_c8.hip) for 3dconv0_1; 0 (default): Winograd F(2,3) along w (conv3d_c8_wino.hip).  3dconv0_1 differs in the last bits (another formula), 3dconv1_0 is the same bits */
+#define MVS_HOOK_COUNT                18
 int mvs_set_test_hook(int id, int value);
 int mvs_get_test_hook(int id);
 

@@ -24,6 +24,10 @@
 //     are summed through 6 KB of LDS when an output plane completes (every second input plane).
 //
 // Operand reads of the next (kw, ci-group, row) step are issued between the MFMAs of the current one.
+//
+// Since the Winograd variant (conv3d_c8_wino.hip: 8 x 32 tiles, one workgroup per CU, 3dconv0_1 as F(2,3) along w) the fused pair
+// takes THAT kernel by default; the fused instantiations below run under MVS_HOOK_PAIR_DIRECT = 1 (A/B runs, tests) and for
+// inputs with a producer BatchNorm (AFF).  The unfused 32 -> 8 kernel (mvs_conv3d_c8_launch) is this file's alone.
 #include "conv_common.h"
 #include <cstdlib>
 #include <cstdio>
@@ -545,11 +549,11 @@ int launch_c8(const ConvArgs& a0, const FuseArgs& fa0, hipStream_t st) {
     if constexpr (FUSE) {
         // SPAN schedule (round 4): groups of G tiles share M workgroups that cut the tiles' concatenated depth into M equal
         // ranges; a range may cross one tile boundary (the workgroup then marches the end of one tile and the start of the
-        // next: two more halo planes and a second prologue).  Taken when it costs fewer plane steps than whole chunks: at the
-        // metric workload 160 tiles x 192 planes meet 512 workgroup slots -- three chunks of 64 leave 32 slots idle (64 + 3
-        // steps), 5 tiles / 16 workgroups fill every slot with ranges of 60 (60 + 3, + 2 across a boundary): 581 -> 565 us,
-        // 921 -> 935 depth maps/s on one box.  Ranges 8 planes shorter across a boundary (62 / 54) and a pairing of long with
-        // short ranges on a CU measured the same (profiles/r04_pair_span_ab.txt).
+        // next: two more halo planes and a second prologue).  Taken when it costs fewer plane steps than whole chunks: with this
+        // kernel's 8 x 16 tiles and two workgroups per CU the metric workload fills every slot with 5 tiles / 16 workgroups in
+        // ranges of 60 planes where whole chunks of 64 leave slots idle (round 4: 581 -> 565 us).  Ranges 8 planes shorter
+        // across a boundary (62 / 54) and a pairing of long with short ranges on a CU measured the same
+        // (profiles/r04_pair_span_ab.txt).  conv3d_c8_wino.hip carries the same schedule at its own tile and residency.
         if (!aff && !mvs_hook(MVS_HOOK_CONV_NO_SPAN) && !hk_planes) {      // (test hook: whole depth chunks, the schedule SPAN replaces)
             const long long chunk_cost = (((long long)tiles * grid.z + 511) / 512) * (a.planes_per_wg + 3);
             int bg = 0, bm = 0; long long bcost = chunk_cost;
@@ -592,7 +596,11 @@ int mvs_conv3d_c8_launch(const ConvArgs& a, hipStream_t st) {
 // Both consumers of a 32-channel volume in one pass: y = conv3d(x, w 32->8, stride 1) as above and
 // y2 = conv3d(x, w2 32->16, stride 2).  Even D, H, W only (SAME pads nothing in front).
 int mvs_conv3d_c8_s2_launch(const ConvArgs& a, const float* w2, float* y2, double* stats2, hipStream_t st,
-                            int slots1, int slots2) {
+                            int slots1, int slots2, const float* wprep_wino) {
     if (a.x2 || a.cout_total != COUT || (a.D & 1) || (a.H & 1) || (a.W & 1)) return MVS_E_SHAPE;
+    // 3dconv0_1 as Winograd F(2,3) along w (conv3d_c8_wino.hip) unless the hook asks for the direct kernel below (A/B runs, tests);
+    // a producer BatchNorm (AFF) has the direct kernel only
+    if (!mvs_hook(MVS_HOOK_PAIR_DIRECT) && !a.xs && !a.bn.stats)
+        return mvs_conv3d_c8_wino_s2_launch(a, wprep_wino, w2, y2, stats2, st, slots1, slots2);
     return launch_c8<true>(a, FuseArgs{w2, y2, stats2, slots1 > 1 ? slots1 : 1, slots2 > 1 ? slots2 : 1}, st);
 }

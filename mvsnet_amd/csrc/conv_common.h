@@ -243,8 +243,15 @@ int mvs_deconv3d_c8_launch(const ConvArgs& a, int Cin, int Cout, hipStream_t st)
 int mvs_conv3d_c8_launch(const ConvArgs& a, hipStream_t st);      // 32 -> 8 stride 1 (conv3d_c8.hip)
 // same + the 32 -> 16 stride-2 consumer of the same input in one pass
 // slots1 / slots2 > 1: the BatchNorm sums go to (slots, 2, C) partial rows (workgroup id modulo slots), see BnSrc::nslot
+// wprep_wino: 3dconv0_1's weights as mvs_conv_wino_weight_layout leaves them (MVS_CONV_WINO_FLOATS floats), or null
 int mvs_conv3d_c8_s2_launch(const ConvArgs& a, const float* w2, float* y2, double* stats2, hipStream_t st,
-                            int slots1 = 1, int slots2 = 1);
+                            int slots1 = 1, int slots2 = 1, const float* wprep_wino = nullptr);
+// the same pass with 3dconv0_1 as Winograd F(2,3) along w (conv3d_c8_wino.hip): what mvs_conv3d_c8_s2_launch takes unless
+// MVS_HOOK_PAIR_DIRECT is set; plain inputs only (no producer BatchNorm)
+constexpr int MVS_CONV_WINO_FLOATS = 3 * 4 * 32 * 3 * 8;      // (kh, point) x ci x (kd, co)
+int mvs_conv_wino_weight_layout(const float* w, float* out, hipStream_t st);
+int mvs_conv3d_c8_wino_s2_launch(const ConvArgs& a, const float* wprep_wino, const float* w2, float* y2, double* stats2,
+                                 hipStream_t st, int slots1, int slots2);
 // output-stationary block kernels of the low-resolution levels (conv3d_os.hip); kind: 0 stride 1, 1 stride 2, 2 transposed
 bool mvs_conv3d_os_covers(int kind, int Cin, int Cout);
 int mvs_conv3d_os_weight_layout(const float* w, int kind, int Cin, int Cout, float* out, hipStream_t st);

@@ -127,6 +127,10 @@ struct RegnetWs {
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// 3dconv0_1's transformed weights for the fused pair's Winograd kernel (conv3d_c8_wino.hip) live behind the other layouts, where the
+// layer has the shape that kernel is built for
+size_t wino_floats(const Net& n) { return (n.ci[L01] == 32 && n.co[L01] == 8) ? (size_t)MVS_CONV_WINO_FLOATS : 0; }
+
 RegnetWs carve(char* base, int D, int H, int W, int b) {
     const size_t v0 = (size_t)D * H * W;
     size_t off = 0;
@@ -154,7 +158,8 @@ extern "C" size_t mvs_regnet_workspace_bytes(int D, int H, int W, int cin, int b
 
 extern "C" size_t mvs_regnet_prepared_floats(int cin, int base) {
     if (cin <= 0 || base <= 0) return 0;
-    return 2 * net_of(cin, base).wtotal;      // fp32 layouts, then bf16 hi|lo layouts
+    const Net n = net_of(cin, base);
+    return 2 * n.wtotal + wino_floats(n);      // fp32 layouts, then bf16 hi|lo layouts, then 3dconv0_1's Winograd layout
 }
 
 extern "C" int mvs_regnet_prepare_f32(const float* const* weights, int cin, int base, float* prepared,
@@ -171,6 +176,7 @@ extern "C" int mvs_regnet_prepare_f32(const float* const* weights, int cin, int 
             if (rc) return rc;
         }
     }
+    if (wino_floats(n)) return mvs_conv_wino_weight_layout(weights[L01], prepared + 2 * n.wtotal, mvs_stream(stream));
     return 0;
 }
 
@@ -231,6 +237,7 @@ struct Run {
     }
     double count(int i) const { return ((double)batch * D * H * W) / (double)(1 << (3 * out_level(i))); }   // voxels behind a statistic
     const float* wprep(int i) const { return (prepared && net.ok[i]) ? prepared + net.woff[i] : nullptr; }
+    const float* wprep_wino() const { return (prepared && wino_floats(net)) ? prepared + 2 * net.wtotal : nullptr; }
     int mark(int l, int k, hipStream_t s) const { return mvs_prof_layers.mark(lp, 2 * l + k, s); }
 };
 
@@ -314,7 +321,7 @@ int fused_pair(Run& r) {
         ConvArgs a = conv_args(r.cost + (size_t)bi * r.D * r.H * r.W * r.net.ci[L01], r.weights[L01], r.ws.y[L01] + wo, r.st(L01),
                                r.D, r.H, r.W, r.net.co[L01]);
         a.wprep = r.wprep(L01);
-        rc = mvs_conv3d_c8_s2_launch(a, r.weights[L10], r.ws.y[L10] + wo, r.st(L10), r.hs, r.PS, r.PS);
+        rc = mvs_conv3d_c8_s2_launch(a, r.weights[L10], r.ws.y[L10] + wo, r.st(L10), r.hs, r.PS, r.PS, r.wprep_wino());
         if (rc) return rc == MVS_E_SHAPE ? APART : rc;
     }
     if ((rc = r.mark(L01, 1, r.hs)) || (rc = mvs_prof_dominant.mark(slot, 1, r.hs))) return rc;
