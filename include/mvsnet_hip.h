@@ -124,7 +124,8 @@ int mvs_get_conv_impl(void);
 #define MVS_HOOK_S1_PLANES            15  /* >= 1: planes per workgroup of the stride-1 plane-march kernels (conv3d_s1_kernel and the unfused 32 -> 8 kernel); 0 (default) = the launcher's choice.  Last bits, as above */
 #define MVS_HOOK_SPAN_FORCE           16  /* G << 8 | M (G = 1..8 tiles per group, M = G..16 ranges): the fused 3dconv0_1 + 1_0 launch takes the SPAN schedule with that pair at any size, if the launcher's other rules allow it (whole chunks if not); 0 (default) = the launcher's choice.  Last bits, as above */
 #define MVS_HOOK_PAIR_DIRECT          17  /* 1: the fused 3dconv0_1 + 1_0 launch takes the direct kernel (conv3d_c8.hip) for 3dconv0_1; 0 (default): Winograd F(2,3) along w (conv3d_c8_wino.hip).  3dconv0_1 differs in the last bits (another formula), 3dconv1_0 is the same bits */
-#define MVS_HOOK_COUNT                18
+#define MVS_HOOK_PAIR_WAVES4          18  /* 1: the Winograd pair kernel runs as four waves per workgroup, each carrying both layers; 0 (default): eight waves, two per SIMD -- waves 0-3 carry 3dconv0_1, waves 4-7 carry 3dconv1_0 and the plane staging.  Same bits */
+#define MVS_HOOK_COUNT                19
 int mvs_set_test_hook(int id, int value);
 int mvs_get_test_hook(int id);
 

@@ -163,11 +163,11 @@ CONV_IMPL = {"auto": 0, "scalar": 1, "mfma": 2, "bf16x3": 3}
 HOOKS = {"cv_tile_rows_log2": 0, "conv_no_span": 1, "conv_no_fuse2": 2, "s2_planes": 3, "gru_one_stream": 4,
          "gru_producer_threads": 5, "unet_persistent": 6, "unet_grid": 7, "fuse2_planes": 8, "regnet_side_branch": 9,
          "out_planes": 10, "bn_slots": 11, "pair_slots": 12, "conv_full_sweeps": 13, "pair_planes": 14, "s1_planes": 15,
-         "span_force": 16, "pair_direct": 17}
+         "span_force": 16, "pair_direct": 17, "pair_waves4": 18}
 HOOK_DEFAULTS = {"cv_tile_rows_log2": -1, "conv_no_span": 0, "conv_no_fuse2": 0, "s2_planes": 0, "gru_one_stream": 0,
                  "gru_producer_threads": 128, "unet_persistent": 1, "unet_grid": 0, "fuse2_planes": 0, "regnet_side_branch": 0,
                  "out_planes": 0, "bn_slots": 0, "pair_slots": 0, "conv_full_sweeps": 0, "pair_planes": 0, "s1_planes": 0,
-                 "span_force": 0, "pair_direct": 0}
+                 "span_force": 0, "pair_direct": 0, "pair_waves4": 0}
 
 _lib = None
 

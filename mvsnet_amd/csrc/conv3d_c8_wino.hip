@@ -10,8 +10,14 @@
 // The kernel is conv3d_c8_kernel<true, false, SPAN> with the tap index kw = 0..2 replaced by the point index 0..3:
 //
 //   * An MFMA column is a pair of output columns, so the workgroup's tile is 8 x 32 (h x w), 10 x 34 staged positions per plane.
-//     Two raw slabs are 87 KB and the 12 (kh, point) weight blocks 36.9 KB: one workgroup (four waves, one per SIMD, the whole
-//     register file) per CU.
+//     Two raw slabs are 87 KB and the 12 (kh, point) weight blocks 36.9 KB: one workgroup per CU.
+//   * The workgroup has eight waves, two per SIMD, in two roles that move no arithmetic between waves: waves 0-3 carry 3dconv0_1
+//     (the Winograd sweep and retire(), 320 MFMAs per interior plane), wave 4 + w carries what wave w carried of 3dconv1_0 (input
+//     channels 8w .. 8w + 7; 72 or 144 MFMAs per plane) and fills the matrix pipe behind its SIMD partner's operand reads,
+//     transforms, stores and barrier waits.  All 512 threads stage the planes, six pieces each.  The role is a scalar branch
+//     around the whole march, so each role's registers are allocated by themselves (at most 256 per wave).  One barrier per
+//     plane joins all eight.  MVS_HOOK_PAIR_WAVES4 = 1 takes the four-wave instantiation (<SPAN, false>): every wave carries both
+//     layers, one wave per SIMD with the whole register file; same bits.
 //   * The slab keeps RAW planes -- the stride-2 part reads them as before.  The B operand of (point, ci group, staged row) is
 //     formed in registers from two ds_read_b128 and one vector add / subtract per k-step.  Even staged columns are stored in
 //     front of odd ones (physical column (c & 1) * 17 + (c >> 1)): the 16 lanes of a read sit at columns 2n + const, which are
@@ -29,7 +35,7 @@
 
 namespace {
 
-constexpr int TW = 32;                         // output columns of a tile = 16 MFMA columns
+constexpr int TW = 32;                        // output columns of a tile = 16 MFMA columns
 constexpr int TH = 8;
 constexpr int PW = TW + 2;                     // 34 staged columns
 constexpr int HP = PW / 2;                     // even columns in front, odd columns behind
@@ -37,7 +43,6 @@ constexpr int CIN = 32, COUT = 8, CQ = CIN / 4;
 constexpr int COUT2 = 16;                      // stride-2 layer
 constexpr int NPOS = (TH + 2) * PW;            // 340 staged positions
 constexpr int NF4 = NPOS * CQ;                 // 2720 float4
-constexpr int NIT = (NF4 + 255) / 256;         // 11
 constexpr int NROWS = 3 * COUT;                // 24
 constexpr int WROW = NROWS * 4;                // floats per (tap, ci-quad)
 constexpr int NPT = 4;                         // Winograd points
@@ -101,8 +106,9 @@ struct WinoArgs {
     int full_sweeps;      // test hook MVS_HOOK_CONV_FULL_SWEEPS, as in conv3d_c8.hip
 };
 
-template <bool SPAN>
-__global__ void __launch_bounds__(256, 1)
+// W8: eight waves, two per SIMD, in two roles (the header comment); false: four waves that each carry both roles
+template <bool SPAN, bool W8>
+__global__ void __launch_bounds__(W8 ? 512 : 256, 1)
 conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* slab = smem;                            // [2][NPOS][SP]
@@ -112,6 +118,7 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar
+    const int rw = W8 ? wave & 3 : wave;           // the wave's index inside its role: row pair (stride 1), ci quarter (stride 2)
     const int n = lane & 15, kq = lane >> 4;
 
     const int tiles_w = (a.W + TW - 1) / TW;
@@ -138,19 +145,24 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
     int d0 = seg_d0[0], d1 = seg_d1[0];
     int T = d1 - d0 + 2;                           // input planes d0-1 .. d1
 
-    if (fa.wprep) copy_weights_to_lds(wl, fa.wprep, W_FLOATS);
-    else for (int i = tid; i < W_FLOATS; i += 256) wl[i] = wino_weight(a.w, i);
-    if (tid < 4) wl[ZOFF + tid] = 0.f;
+    // (by the 256 threads of the stride-1 role: W8's other half fetches its wS fragments and stages the first plane meanwhile)
+    auto init_weights = [&]() __attribute__((always_inline)) {
+        if (fa.wprep) copy_weights_to_lds(wl, fa.wprep, W_FLOATS);
+        else for (int i = tid; i < W_FLOATS; i += 256) wl[i] = wino_weight(a.w, i);
+        if (tid < 4) wl[ZOFF + tid] = 0.f;
+    };
 
     // ---- staging ---------------------------------------------------------------------------------
+    // every thread of the workgroup stages: 11 pieces of a plane with four waves, 6 with eight
+    constexpr int NTH = W8 ? 512 : 256, NITW = (NF4 + NTH - 1) / NTH;
     const int c4 = tid % CQ;
-    float4 pre[NIT];
-    int goff[NIT], loff[NIT];
+    float4 pre[NITW];
+    int goff[NITW], loff[NITW];
     auto set_goff = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            int f = tid + 256 * i;
-            if (f >= NF4) f -= 256;                // spare threads of the last piece redo their previous one
+        for (int i = 0; i < NITW; ++i) {
+            int f = tid + NTH * i;
+            if (f >= NF4) f -= NTH;                // spare threads of the last piece redo their previous one
             int pos = f / CQ;
             int r = pos / PW, c = pos - r * PW;
             int gh = h0 - 1 + r, gw = w0 - 1 + c;
@@ -159,7 +171,6 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
             loff[i] = slab_off(r, c, c4);
         }
     };
-    set_goff();
     // Buffer addressing (the launcher guarantees < 2 GB tensors): 32-bit byte offsets, and an offset
     // with bit 31 set is out of range -> loads return 0 (= SAME padding), stores are dropped.
     const int plane_bytes = a.H * a.W * CIN * 4;
@@ -187,10 +198,10 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
         for (int i = 0; i < 3; ++i) acc[p][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
 
-    // raw operand d_c: staged row 2*wave + i (i = 0..3, an immediate), column 2n + c, slot kq (s = 1 is ^16)
+    // raw operand d_c: staged row 2*rw + i (i = 0..3, an immediate), column 2n + c, slot kq (s = 1 is ^16)
     int bcol[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) bcol[c] = slab_off(2 * wave, 2 * n + c, kq);
+    for (int c = 0; c < 4; ++c) bcol[c] = slab_off(2 * rw, 2 * n + c, kq);
     const int hi = n >> 3;                         // 0: tile rows 0-7, 1: rows 8-15
     const int a_lane = (kq * NROWS + (n & 7)) * 4;
 
@@ -227,8 +238,8 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) load_grp(0, r);
         form(0);
-        // One wave per SIMD: nothing else fills the matrix pipe while this wave issues anything but an MFMA.  So the next step's
-        // operand reads, its add / subtract and the staging piece are spread over the four k-steps of the current one, each
+        // Four waves: nothing else fills the matrix pipe while this wave issues anything but an MFMA (with eight, the SIMD's
+        // stride-2 wave does).  So the next step's operand reads, its add / subtract and the staging piece are spread over the four k-steps of the current one, each
         // behind a group of 2-3 MFMAs (64-96 clocks of matrix work): raw operands after k-step 0, weights after k-step 1, the
         // transformed operand (its reads are two MFMA groups old by then) after k-step 2, staging after k-step 3.
 #pragma unroll
@@ -264,12 +275,11 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
     int yoff[3];
     auto set_yoff = [&]() __attribute__((always_inline)) {
         const int w = w0 + 2 * n, co = 4 * (kq & 1);
-        const int hs[3] = {h0 + 2 * wave, h0 + 2 * wave + 1, h0 + 2 * wave + (kq >> 1)};
+        const int hs[3] = {h0 + 2 * rw, h0 + 2 * rw + 1, h0 + 2 * rw + (kq >> 1)};
 #pragma unroll
         for (int i = 0; i < 3; ++i)
             yoff[i] = (hs[i] < a.H && w < a.W) ? ((hs[i] * a.W + w) * COUT + co) * 4 : OOB;
     };
-    set_yoff();
     const int yplane_bytes = a.H * a.W * COUT * 4;
     auto retire = [&](auto Pc, int o) __attribute__((always_inline)) {
         constexpr int P = decltype(Pc)::value;
@@ -306,29 +316,33 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
     // ---- stride-2 part ---------------------------------------------------------------------------
     // Column tile ct = (rt, wt), lane column n: output (oh, ow) = (h0/2 + 2rt + (n>>3), w0/2 + 8wt + (n&7)); input tap
     // (kh, kw) sits at staged (row 4rt + 2(n>>3) + kh + 1, col 16wt + 2(n&7) + kw + 1).  This wave's k index
-    // kq of step j is input channel 8*wave + 2kq + j (one ds_read_b64 per tap and tile).
+    // kq of step j is input channel 8*rw + 2kq + j (one ds_read_b64 per tap and tile).
     float wS[3][9][2];
     f32x4 cur[NCT], prv[NCT];                      // output planes od_cur / od_cur - 1, per column tile
     int s2b[3][2];
     float st2_s[4] = {0.f, 0.f, 0.f, 0.f}, st2_q[4] = {0.f, 0.f, 0.f, 0.f};
     int fin_od = -1;                               // output plane whose partial tiles wait in `red`
     const int Ho = a.H / 2, Wo = a.W / 2;
+    auto init_s2 = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int kd = 0; kd < 3; ++kd)
+        for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
+            for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-                wS[kd][tap][j] = fa.w2[((size_t)(kd * 9 + tap) * CIN + 8 * wave + 2 * kq + j) * COUT2 + n];
+                for (int j = 0; j < 2; ++j)
+                    wS[kd][tap][j] = fa.w2[((size_t)(kd * 9 + tap) * CIN + 8 * rw + 2 * kq + j) * COUT2 + n];
 #pragma unroll
-    for (int kw = 0; kw < 3; ++kw)
+        for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
-        for (int wt = 0; wt < 2; ++wt)
-            s2b[kw][wt] = slab_off(2 * (n >> 3), 16 * wt + 2 * (n & 7) + kw + 1, 2 * wave + (kq >> 1)) + 2 * (kq & 1);
+            for (int wt = 0; wt < 2; ++wt)
+                s2b[kw][wt] = slab_off(2 * (n >> 3), 16 * wt + 2 * (n & 7) + kw + 1, 2 * rw + (kq >> 1)) + 2 * (kq & 1);
 #pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) { cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; prv[ct] = cur[ct]; }
+        for (int ct = 0; ct < NCT; ++ct) { cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; prv[ct] = cur[ct]; }
+    };
 
-    auto s2_sweep = [&](auto Ec, const float* buf) __attribute__((always_inline)) {
+    // `extra2(tap)` is called once per tap: with eight waves the plane staging hangs on it, as it hangs on the sweep's extra(G)
+    // with four
+    auto s2_sweep = [&](auto Ec, const float* buf, auto&& extra2) __attribute__((always_inline)) {
         // 0: odd plane, kd 1 -> cur;  1: even plane, kd 0 -> cur, kd 2 -> prv;  2: the even plane that ends a range, kd 2 -> prv
         // only (the output plane it would start belongs to the next range)
         constexpr int MODE = decltype(Ec)::value;
@@ -354,21 +368,23 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
                         cur[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wS[1][tap][j], bval, cur[ct], 0, 0, 0);
                     }
                 }
+            extra2(tap);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    // the waves' K-quarters of the output plane that has just completed -> `red`, summed by wave 0 after the next barrier
+    // the waves' K-quarters of the output plane that has just completed -> `red`, summed by the role's first wave after the next
+    // barrier
     auto s2_park = [&](int od) __attribute__((always_inline)) {
-        if (wave > 0) {
+        if (rw > 0) {
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct)
-                *(f32x4*)(red + (((wave - 1) * NCT + ct) * 64 + lane) * 4) = prv[ct];
+                *(f32x4*)(red + (((rw - 1) * NCT + ct) * 64 + lane) * 4) = prv[ct];
         }
         fin_od = od;
     };
-    // wave 0: sum the four K-quarters of output plane fin_od, store, BatchNorm sums
+    // the role's first wave: sum the four K-quarters of output plane fin_od, store, BatchNorm sums
     auto s2_finish = [&]() __attribute__((always_inline)) {
-        if (fin_od >= 0 && wave == 0) {
+        if (fin_od >= 0 && rw == 0) {
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
                 f32x4 r = prv[ct];
@@ -390,127 +406,191 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
     };
 
     // ---- plane march (conv3d_c8.hip: same steps, same halo-plane rules) ---------------------------
-    // Plane q is swept while plane q+1 moves registers -> LDS (steps 4..14) and plane q+2 is requested from global memory
-    // (steps 16..26).  A range [d0, d1) stages the input planes d0 - 1 .. d1 (t = 0 .. T - 1, P = t % 3); its first plane issues
+    // Plane q is swept while plane q+1 moves registers -> LDS (steps 4..14 with four waves) and plane q+2 is requested from global
+    // memory (steps 16..26).  A range [d0, d1) stages the input planes d0 - 1 .. d1 (t = 0 .. T - 1, P = t % 3); its first plane issues
     // only the tiles acc[.][0] | acc[.][1] (kd = 0 of output d0), its last only the block that retires (kd = 2 of output d1 - 1)
     // and the kd = 2 half of the stride-2 part; planes outside the volume issue nothing.  fa.full_sweeps = 1 runs plane() on all
     // T planes, 2 on all inside the volume.
-    auto prologue = [&](int t0) __attribute__((always_inline)) {
-        float* buf = slab + (t0 & 1) * SLAB_FLOATS;
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) load_piece(i, d0 - 1 + t0);
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) stage_piece(i, buf);
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) load_piece(i, d0 + t0);
-        __syncthreads();
-    };
+    //
+    // The whole march is written once per ROLE: 0 = both layers in every wave (four waves), 1 = the stride-1 layer alone (waves
+    // 0-3 of eight), 2 = the stride-2 layer alone (waves 4-7 of eight).  Every role passes the same barriers: the prologue's and
+    // one per plane.  Every thread stages its NITW pieces of a plane in every role (all of them on waves 4-7 took 256 registers
+    // and 29-44 spilled ones).  Roles 0 and 1 hang them on the sweep's extra(G); role 2 hangs them between the stride-2 taps
+    // (extra2), and on a plane without a stride-2 sweep -- outside the volume, before the range's first stride-2 plane, a
+    // first_plane -- it stages them in a row.
+    auto march = [&](auto Rc) __attribute__((always_inline)) {
+        constexpr int ROLE = decltype(Rc)::value;
+        constexpr bool S1 = ROLE != 2, S2 = ROLE != 1;
+        if (S1) {
+            init_weights();
+            set_yoff();      // (a raised issue priority for role 1 from here on measured a tie: EXPERIMENTS, pair-roles addendum)
+        }
+        set_goff();
+        if (S2) init_s2();
 
-    auto plane = [&](auto Pc, int t) __attribute__((always_inline)) {
-        const int q = d0 - 1 + t;
-        float* cur_buf = slab + (t & 1) * SLAB_FLOATS;
-        float* nxt = slab + ((t + 1) & 1) * SLAB_FLOATS;
-        const bool in_vol = (q >= 0) && (q < a.D);
-        // (past the last plane these stage / request planes nobody reads: harmless, and branch-free)
-        auto extra = [&](int G) __attribute__((always_inline)) {
-            if (G >= 4 && G < 4 + NIT) stage_piece(G - 4, nxt);
-            if (G >= 16 && G < 16 + NIT) load_piece(G - 16, q + 2);
+        auto prologue = [&](int t0) __attribute__((always_inline)) {
+            float* buf = slab + (t0 & 1) * SLAB_FLOATS;
+#pragma unroll
+            for (int i = 0; i < NITW; ++i) load_piece(i, d0 - 1 + t0);
+#pragma unroll
+            for (int i = 0; i < NITW; ++i) stage_piece(i, buf);
+#pragma unroll
+            for (int i = 0; i < NITW; ++i) load_piece(i, d0 + t0);
+            __syncthreads();
         };
-        s2_finish();
-        sweep(Pc, std::integral_constant<int, 7>{}, cur_buf, extra);      // planes outside the volume are staged as zeros
-        if (q >= d0) {
-            if (q & 1) {
-                if (in_vol) s2_sweep(std::false_type{}, cur_buf);
-            } else {
-                // plane q = 2*od_cur: od_cur starts (kd 0), od_cur - 1 completes (kd 2)
+        // staging of the plane after the one being swept: item k < NITW moves piece k registers -> LDS, item NITW + k requests
+        // piece k of the plane after that (past the last plane these stage / request planes nobody reads: harmless, and branch-free)
+        auto stage_item = [&](int k, float* nxt, int q) __attribute__((always_inline)) {
+            if (k < NITW) stage_piece(k, nxt); else load_piece(k - NITW, q + 2);
+        };
+        auto stage_all = [&](float* nxt, int q) __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < 2 * NITW; ++k) stage_item(k, nxt, q);
+        };
+
+        auto plane = [&](auto Pc, int t) __attribute__((always_inline)) {
+            const int q = d0 - 1 + t;
+            float* cur_buf = slab + (t & 1) * SLAB_FLOATS;
+            float* nxt = slab + ((t + 1) & 1) * SLAB_FLOATS;
+            const bool in_vol = (q >= 0) && (q < a.D);
+            auto extra = [&](int G) __attribute__((always_inline)) {
+                if (S1) {
+                    if (G >= 4 && G < 4 + NITW) stage_piece(G - 4, nxt);
+                    if (G >= 16 && G < 16 + NITW) load_piece(G - 16, q + 2);
+                }
+            };
+            // role 2: the 12 items over the nine taps, 1-2 behind each tap's 8 or 16 MFMAs
+            auto extra2 = [&](int tap) __attribute__((always_inline)) {
+                if (ROLE == 2) {
+#pragma unroll
+                    for (int k = 0; k < 2 * NITW; ++k)
+                        if (k >= tap * 2 * NITW / 9 && k < (tap + 1) * 2 * NITW / 9) stage_item(k, nxt, q);
+                }
+            };
+            if (S2) s2_finish();
+            if (S1) sweep(Pc, std::integral_constant<int, 7>{}, cur_buf, extra);      // planes outside the volume are staged as zeros
+            if (S2) {
+                const bool even = q >= d0 && !(q & 1);
+                const bool swept = q >= d0 && in_vol;
+                if (even) {
+                    // plane q = 2*od_cur: od_cur starts (kd 0), od_cur - 1 completes (kd 2)
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) { prv[ct] = cur[ct]; cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+                }
+                if (swept) {
+                    if (q & 1) s2_sweep(std::false_type{}, cur_buf, extra2);
+                    else s2_sweep(std::true_type{}, cur_buf, extra2);
+                } else if (ROLE == 2) {
+                    stage_all(nxt, q);
+                }
+                if (even) {
+                    const int od_prev = q / 2 - 1;
+                    if (2 * od_prev >= d0) s2_park(od_prev);
+                }
+            }
+            if (S1) retire(Pc, q - 1);
+            __syncthreads();
+        };
+        // t = 0 of a range that starts inside the volume (P = 0)
+        auto first_plane = [&]() __attribute__((always_inline)) {
+            const int q = d0 - 1;
+            float* nxt = slab + SLAB_FLOATS;
+            auto extra = [&](int G) __attribute__((always_inline)) {
+                if (S1) {
+                    if (G >= 4 && G < 4 + NITW) stage_piece(G - 4, nxt);
+                    if (G >= 16 && G < 16 + NITW) load_piece(G - 16, q + 2);
+                }
+            };
+            if (S1) {
+                sweep(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, slab, extra);
+                retire(std::integral_constant<int, 0>{}, q - 1);      // (zeroes what block 1 took)
+            }
+            if (ROLE == 2) stage_all(nxt, q);
+            __syncthreads();
+        };
+        // t = T - 1, plane d1
+        auto last_plane = [&](auto Pc) __attribute__((always_inline)) {
+            constexpr int P = decltype(Pc)::value;
+            const int q = d1;
+            const float* cur_buf = slab + ((T - 1) & 1) * SLAB_FLOATS;
+            const bool in_vol = q < a.D;
+            if (S2) s2_finish();
+            if (S1 && in_vol) sweep(Pc, std::integral_constant<int, (P + 1) % 3 == 2 ? 4 : 3>{}, cur_buf, [](int) {});
+            if (S2) {
+                // plane q = 2*od_cur completes od_cur - 1 (kd 2); od_cur is another range's
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) { prv[ct] = cur[ct]; cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-                if (in_vol) s2_sweep(std::true_type{}, cur_buf);
+                if (in_vol) s2_sweep(std::integral_constant<int, 2>{}, cur_buf, [](int) {});
                 const int od_prev = q / 2 - 1;
                 if (2 * od_prev >= d0) s2_park(od_prev);
             }
-        }
-        retire(Pc, q - 1);
-        __syncthreads();
-    };
-    // t = 0 of a range that starts inside the volume (P = 0)
-    auto first_plane = [&]() __attribute__((always_inline)) {
-        const int q = d0 - 1;
-        float* nxt = slab + SLAB_FLOATS;
-        auto extra = [&](int G) __attribute__((always_inline)) {
-            if (G >= 4 && G < 4 + NIT) stage_piece(G - 4, nxt);
-            if (G >= 16 && G < 16 + NIT) load_piece(G - 16, q + 2);
+            if (S1) retire(Pc, q - 1);
+            __syncthreads();
         };
-        sweep(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, slab, extra);
-        retire(std::integral_constant<int, 0>{}, q - 1);      // (zeroes what block 1 took)
-        __syncthreads();
-    };
-    // t = T - 1, plane d1
-    auto last_plane = [&](auto Pc) __attribute__((always_inline)) {
-        constexpr int P = decltype(Pc)::value;
-        const int q = d1;
-        const float* cur_buf = slab + ((T - 1) & 1) * SLAB_FLOATS;
-        const bool in_vol = q < a.D;
-        s2_finish();
-        if (in_vol) sweep(Pc, std::integral_constant<int, (P + 1) % 3 == 2 ? 4 : 3>{}, cur_buf, [](int) {});
-        // plane q = 2*od_cur completes od_cur - 1 (kd 2); od_cur is another range's
+        for (int sg = 0; sg < (SPAN ? nseg : 1); ++sg) {
+            if (SPAN && sg > 0) {
+                // second segment: another tile, its first planes.  Whatever the first march left in the accumulators belongs to
+                // planes past its range; the last stride-2 plane of the first range is flushed before its partials are
+                // overwritten.  Each role resets its own state.
+                if (S2) s2_finish();
+                h0 = (seg_tile[1] / tiles_w) * TH; w0 = (seg_tile[1] % tiles_w) * TW;
+                d0 = seg_d0[1]; d1 = seg_d1[1]; T = d1 - d0 + 2;
+                set_goff();
+                if (S1) {
+                    set_yoff();
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) { prv[ct] = cur[ct]; cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        if (in_vol) s2_sweep(std::integral_constant<int, 2>{}, cur_buf);
-        const int od_prev = q / 2 - 1;
-        if (2 * od_prev >= d0) s2_park(od_prev);
-        retire(Pc, q - 1);
-        __syncthreads();
-    };
-    for (int sg = 0; sg < (SPAN ? nseg : 1); ++sg) {
-        if (SPAN && sg > 0) {
-            // second segment: another tile, its first planes.  Whatever the first march left in the accumulators belongs to
-            // planes past its range; the last stride-2 plane of the first range is flushed before its partials are overwritten.
-            s2_finish();
-            h0 = (seg_tile[1] / tiles_w) * TH; w0 = (seg_tile[1] % tiles_w) * TW;
-            d0 = seg_d0[1]; d1 = seg_d1[1]; T = d1 - d0 + 2;
-            set_goff(); set_yoff();
+                    for (int p = 0; p < NPT; ++p)
 #pragma unroll
-            for (int p = 0; p < NPT; ++p)
+                        for (int i = 0; i < 3; ++i) acc[p][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+                if (S2) {
 #pragma unroll
-                for (int i = 0; i < 3; ++i) acc[p][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) { cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; prv[ct] = cur[ct]; }
-        }
-        // planes [t_lo, t_hi) run plane(); T >= 3, so the first and the last plane are two planes
-        const bool trim_first = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d0 == 0);
-        const bool trim_last = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d1 == a.D);
-        const int t_lo = trim_first ? 1 : 0, t_hi = trim_last ? T - 1 : T;
-        prologue(trim_first && d0 == 0 ? 1 : 0);
-        if (trim_first && d0 > 0) first_plane();
-        for (int t = 0; t < t_hi; t += 3) {
-            if (t >= t_lo) plane(std::integral_constant<int, 0>{}, t);
-            if (t + 1 < t_hi) plane(std::integral_constant<int, 1>{}, t + 1);
-            if (t + 2 < t_hi) plane(std::integral_constant<int, 2>{}, t + 2);
-        }
-        if (trim_last) {
-            const int pl = (T - 1) % 3;
-            if (pl == 0) last_plane(std::integral_constant<int, 0>{});
-            else if (pl == 1) last_plane(std::integral_constant<int, 1>{});
-            else last_plane(std::integral_constant<int, 2>{});
-        }
-    }
-    s2_finish();
-    if (fa.stats2 && wave == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float sv = st2_s[k], qv = st2_q[k];
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) { sv += __shfl_xor(sv, o, 64); qv += __shfl_xor(qv, o, 64); }
-            if (n == 0) {
-                double* s2p = fa.stats2 + (size_t)((blockIdx.x + gridDim.x * blockIdx.z) % fa.slots2) * 2 * COUT2;
-                atomicAdd(&s2p[4 * kq + k], (double)sv);
-                atomicAdd(&s2p[COUT2 + 4 * kq + k], (double)qv);
+                    for (int ct = 0; ct < NCT; ++ct) { cur[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; prv[ct] = cur[ct]; }
+                }
+            }
+            // planes [t_lo, t_hi) run plane(); T >= 3, so the first and the last plane are two planes
+            const bool trim_first = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d0 == 0);
+            const bool trim_last = fa.full_sweeps == 0 || (fa.full_sweeps == 2 && d1 == a.D);
+            const int t_lo = trim_first ? 1 : 0, t_hi = trim_last ? T - 1 : T;
+            prologue(trim_first && d0 == 0 ? 1 : 0);
+            if (trim_first && d0 > 0) first_plane();
+            for (int t = 0; t < t_hi; t += 3) {
+                if (t >= t_lo) plane(std::integral_constant<int, 0>{}, t);
+                if (t + 1 < t_hi) plane(std::integral_constant<int, 1>{}, t + 1);
+                if (t + 2 < t_hi) plane(std::integral_constant<int, 2>{}, t + 2);
+            }
+            if (trim_last) {
+                const int pl = (T - 1) % 3;
+                if (pl == 0) last_plane(std::integral_constant<int, 0>{});
+                else if (pl == 1) last_plane(std::integral_constant<int, 1>{});
+                else last_plane(std::integral_constant<int, 2>{});
             }
         }
-    }
+        if (S2) {
+            s2_finish();
+            // 3dconv1_0's sums stay on the wave that finished the tiles
+            if (fa.stats2 && rw == 0) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float sv = st2_s[k], qv = st2_q[k];
+#pragma unroll
+                    for (int o = 8; o > 0; o >>= 1) { sv += __shfl_xor(sv, o, 64); qv += __shfl_xor(qv, o, 64); }
+                    if (n == 0) {
+                        double* s2p = fa.stats2 + (size_t)((blockIdx.x + gridDim.x * blockIdx.z) % fa.slots2) * 2 * COUT2;
+                        atomicAdd(&s2p[4 * kq + k], (double)sv);
+                        atomicAdd(&s2p[COUT2 + 4 * kq + k], (double)qv);
+                    }
+                }
+            }
+        }
+    };
+    // (a scalar branch: each role's registers are allocated by themselves, the kernel takes the larger set)
+    if (!W8) march(std::integral_constant<int, 0>{});
+    else if (wave < 4) march(std::integral_constant<int, 1>{});
+    else march(std::integral_constant<int, 2>{});
 
-    // every lane's st_* are the sums of channels 4*(kq&1) .. +3: fold lanes l and l^32
+    // every lane's st_* are the sums of channels 4*(kq&1) .. +3: fold lanes l and l^32.  stats_commit adds the rows of waves 0-3;
+    // with eight waves the other four pass zeros into rows 4-7 (8 x 32 floats of the slab, which is dead by now)
     if (a.stats) stats_commit<COUT>(st_s, st_q, true, slab,
                                     a.stats + (size_t)((blockIdx.x + gridDim.x * blockIdx.z) % fa.slots1) * 2 * COUT,
                                     a.cout_total, 0);
@@ -550,13 +630,16 @@ int mvs_conv3d_c8_wino_s2_launch(const ConvArgs& a0, const float* wprep_wino, co
     const size_t smem = (size_t)LDS_FLOATS * sizeof(float);
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3d_c8_wino_kernel<false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3d_c8_wino_kernel<true>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
+        const void* kernels[4] = {(const void*)conv3d_c8_wino_kernel<false, false>, (const void*)conv3d_c8_wino_kernel<true, false>,
+                                  (const void*)conv3d_c8_wino_kernel<false, true>, (const void*)conv3d_c8_wino_kernel<true, true>};
+        for (const void* k : kernels) {
+            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            if (e != hipSuccess) return (int)e;
+        }
         attr_done = true;
     }
+    // eight waves in two roles unless the test hook asks for the four-wave instantiation (same bits)
+    const bool w8 = !mvs_hook(MVS_HOOK_PAIR_WAVES4);
     // SPAN schedule: groups of G tiles share M workgroups that cut the tiles' concatenated depth into M equal ranges; a range may
     // cross one tile boundary.  Taken when it costs fewer plane steps than whole chunks.
     if (!mvs_hook(MVS_HOOK_CONV_NO_SPAN) && !hk_planes) {      // (test hook: whole depth chunks, the schedule SPAN replaces)
@@ -580,10 +663,12 @@ int mvs_conv3d_c8_wino_s2_launch(const ConvArgs& a0, const float* wprep_wino, co
         if (bg) {
             fa.span_g = bg; fa.span_m = bm;
             for (int k = 0; k <= bm; ++k) fa.span_b[k] = k * (bg * a.D / bm);
-            conv3d_c8_wino_kernel<true><<<dim3((tiles / bg) * bm), 256, smem, st>>>(a, fa);
+            if (w8) conv3d_c8_wino_kernel<true, true><<<dim3((tiles / bg) * bm), 512, smem, st>>>(a, fa);
+            else conv3d_c8_wino_kernel<true, false><<<dim3((tiles / bg) * bm), 256, smem, st>>>(a, fa);
             return (int)hipGetLastError();
         }
     }
-    conv3d_c8_wino_kernel<false><<<grid, 256, smem, st>>>(a, fa);
+    if (w8) conv3d_c8_wino_kernel<false, true><<<grid, 512, smem, st>>>(a, fa);
+    else conv3d_c8_wino_kernel<false, false><<<grid, 256, smem, st>>>(a, fa);
     return (int)hipGetLastError();
 }

@@ -27,13 +27,17 @@ extern "C" int mvs_get_conv_impl(void) { return g_conv_impl; }
 #ifndef MVS_PAIR_DIRECT_DEFAULT      // A/B builds: -DMVS_PAIR_DIRECT_DEFAULT=1 is this library with the direct pair kernel as its default
 #define MVS_PAIR_DIRECT_DEFAULT 0
 #endif
-std::atomic<int> mvs_hooks[MVS_HOOK_COUNT] = {{-1}, {0}, {0}, {0}, {0}, {128}, {1}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {MVS_PAIR_DIRECT_DEFAULT}};
+#ifndef MVS_PAIR_WAVES4_DEFAULT      // A/B builds: -DMVS_PAIR_WAVES4_DEFAULT=1 is this library with the four-wave Winograd pair kernel as its default
+#define MVS_PAIR_WAVES4_DEFAULT 0
+#endif
+std::atomic<int> mvs_hooks[MVS_HOOK_COUNT] = {{-1}, {0}, {0}, {0}, {0}, {128}, {1}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {MVS_PAIR_DIRECT_DEFAULT},
+                                              {MVS_PAIR_WAVES4_DEFAULT}};
 extern "C" int mvs_set_test_hook(int id, int value) {
     bool ok = false;
     switch (id) {
         case MVS_HOOK_CV_TILE_ROWS_LOG2: ok = value >= -1 && value <= 3; break;
         case MVS_HOOK_CONV_NO_SPAN: case MVS_HOOK_CONV_NO_FUSE2: case MVS_HOOK_GRU_ONE_STREAM: case MVS_HOOK_UNET_PERSISTENT:
-        case MVS_HOOK_REGNET_SIDE_BRANCH: case MVS_HOOK_PAIR_DIRECT:
+        case MVS_HOOK_REGNET_SIDE_BRANCH: case MVS_HOOK_PAIR_DIRECT: case MVS_HOOK_PAIR_WAVES4:
             ok = value == 0 || value == 1; break;
         case MVS_HOOK_CONV_FULL_SWEEPS: ok = value >= 0 && value < 16 && (value & 3) < 3 && (value >> 2) < 3; break;
         case MVS_HOOK_UNET_GRID: ok = value >= 0 && value <= 65536; break;
