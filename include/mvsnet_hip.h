@@ -956,6 +956,30 @@ int mvs_mesh_cluster_mark_i32(const int* cluster_faces, long long M, long long F
                               const long long* sorted_hi, const long long* order, int* face_keep, int* vertex_keep,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* Sampling of a triangle mesh's surface into a point cloud (csrc/mesh_sample.hip; semantics in mvsnet_amd/mesh_sample.py).
+ * M vertices, 0..2^31-1, and F faces, 0..2^26 (negative: MVS_E_BADARG, beyond: MVS_E_SHAPE); a pointer to an array of M or F
+ * entries may be NULL when that size is 0.
+ *   mvs_mesh_sample_quota_f32   vertices (M,3) float32, faces (F,3) int32, density (samples per unit area, finite and > 0, else
+ *                 MVS_E_BADARG) -> quota (F) int64: floor(area * density * 2^16), 0 for a face that is invalid (an index outside
+ *                 0..M-1 or a vertex that is not finite), has no area or is saturated (2^36 or more).  Clears the status words
+ *                 and counts words 0 (invalid), 1 (zero area) and 2 (saturated)
+ *   (an inclusive int64 scan of quota -> sums (F); the number of samples is N = sums[F - 1] >> 16)
+ *   mvs_mesh_sample_write_f32   colours NULL or (M,3) uint8; sums (F) int64; N samples, 0..2^31-1; seed, any 64 bits ->
+ *                 out_xyz (N,3) float32 and, each unless NULL, out_face (N) int32, out_colours (N,3) uint8 (needs colours, else
+ *                 MVS_E_BADARG) and out_normals (N,3) float32.  Sample g lies in the first face f with (sums[f] >> 16) > g.  Sums
+ *                 that are not the scan of the quota give zeros and face -1 for the samples that find no face with indices
+ *                 inside 0..M-1: every index read from sums or faces is range-checked before it is used
+ *   workspace     mvs_mesh_sample_workspace_bytes(M, F) bytes (0 for invalid sizes): 64 int32 status words
+ * Both only enqueue on `stream`: nothing is allocated, nothing synchronised.  The only atomics are integer counts, and a sample
+ * depends on (seed, g) and its face alone: the same inputs give the same bytes on any grid.  Every argument is checked before
+ * the first GPU call and the outputs are untouched on error. */
+size_t mvs_mesh_sample_workspace_bytes(long long M, long long F);
+int mvs_mesh_sample_quota_f32(const float* vertices, long long M, const int* faces, long long F, double density, long long* quota,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mvs_mesh_sample_write_f32(const float* vertices, const unsigned char* colours, long long M, const int* faces, long long F,
+                              const long long* sums, long long N, unsigned long long seed, float* out_xyz, int* out_face,
+                              unsigned char* out_colours, float* out_normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,11 @@ SIGNATURES = {
     "mvs_mesh_cluster_sums_f32": (_i, [_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _p, _p, _p, _p, _sz, _p]),
     "mvs_mesh_cluster_faces_i32": (_i, [_p, _ll, _ll, _p, _p, _p, _p, _p, _sz, _p]),
     "mvs_mesh_cluster_mark_i32": (_i, [_p, _ll, _ll, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # surface sampling (csrc/mesh_sample.hip), before mvs_fusion_workspace_bytes for the same reason; its arena cases and pin are
+    # tests/test_gpu_arena_mesh_sample.py
+    "mvs_mesh_sample_workspace_bytes": (_sz, [_ll, _ll]),
+    "mvs_mesh_sample_quota_f32": (_i, [_p, _ll, _p, _ll, C.c_double, _p, _p, _sz, _p]),
+    "mvs_mesh_sample_write_f32": (_i, [_p, _p, _ll, _p, _ll, _p, _ll, C.c_ulonglong, _p, _p, _p, _p, _p]),
     "mvs_fusion_workspace_bytes": (_sz, [_i] * 5),
     "mvs_fusion_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "mvs_depth_normals_f32": (_i, [_p, _p, _i, _i, _i, _p, _f, _f, _p, _p]),

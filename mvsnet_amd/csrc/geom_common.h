@@ -69,6 +69,24 @@ __device__ int geo_block_exclusive_scan(int v, int* sh, int& total) {
     return incl - v;
 }
 
+// Sum of one int per thread over a workgroup of THREADS threads: a wave sum by shuffles, then THREADS / 64 words of LDS.  The
+// total is returned in thread 0 (other threads get a partial sum).  Every thread calls it; `sh` holds THREADS / 64 ints, and
+// a second call on the same `sh` needs a __syncthreads() in between.  A kernel that counts into a status word adds thread
+// 0's total with ONE atomic per workgroup (a wave, an atomic measured 0.37 -> 0.045 ms on 2 M faces: DESIGN 4.17).
+template <int THREADS>
+__device__ __forceinline__ int geo_block_sum(int v, int* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int total = 0;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 0; w < THREADS / 64; ++w) total += sh[w];
+    }
+    return total;
+}
+
 namespace {
 
 // One lane per pixel of all views: keys -> depth (0 where empty) and index (-1 where empty).  index may be NULL.

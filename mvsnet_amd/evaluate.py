@@ -3,6 +3,7 @@
     python -m mvsnet_amd.evaluate --pred P.ply --gt G.ply --max_dist 20 [--thresholds 0.5,1,2]
         [--crop x0,y0,z0,x1,y1,z1] [--transform T.txt] [--voxel_pred s] [--voxel_gt s] [--out metrics.json]
         [--dump_distances DIR] [--align icp --align_stages 4:8:30,2:4:30,0:2:30 [--align_with_scale]]
+        [--pred_spacing s] [--gt_spacing s]
 
 The nearest-neighbour searches, the voxel downsampling and the statistics are HIP kernels (csrc/pointcloud.hip); torch owns
 the device memory, the stable key sort of the downsampling and the transform / crop arithmetic.
@@ -32,6 +33,10 @@ truth, each (n,3) float32.
     two companions the same over G; overall = (accuracy + completeness) / 2 (None when a mean has no inlier);
     for each tau of `thresholds` (0 < tau <= max_dist, ValueError otherwise): precision = #{p : d(p) < tau} / |P|,
     recall = #{g : d(g) < tau} / |G|, fscore = 2 precision recall / (precision + recall), 0 when both are 0.
+  * Meshes (pred_faces / gt_faces with pred_spacing / gt_spacing, optional; off by default and then nothing here changes).
+    That side is a triangle mesh: its cloud is the surface samples of mvsnet_amd.mesh_sample at density 1 / spacing^2 (seed
+    0), taken before everything else, so the alignment, the transform, the crop and the voxel filter apply to the samples as
+    they do to points.  The metrics gain "pred_sampling" / "gt_sampling": the spacing and the sampling's stats.
   * Sums are float64 and counts integers, reduced in a fixed order: the same inputs give bit-identical metrics and distance
     arrays on every run (no float atomics).
 """
@@ -329,6 +334,26 @@ def choose_grid(target, max_dist, cell=None):
     return {"origin": [float(v) for v in lo.cpu().numpy()], "cell": float(np.float32(cell)), "dims": [int(d) for d in dims]}
 
 
+def _surface(points, faces, spacing, name, device):
+    """A side of the evaluation that is a mesh -> (its surface samples as a device tensor, {"spacing", stats...}); a side
+    without faces and spacing -> (points, None), untouched."""
+    if faces is None and spacing is None:
+        return points, None
+    if faces is None or spacing is None:
+        raise ValueError("%s_faces and %s_spacing go together" % (name, name))
+    import torch
+    from . import _lib, mesh_sample
+    from .mesh_clean import _inputs
+    density = mesh_sample.check_spacing(spacing)
+    if not hasattr(points, "shape") or not hasattr(faces, "shape"):
+        raise ValueError("%s and %s_faces must be arrays or tensors" % (name, name))
+    mesh_sample._shapes(points, None, faces)
+    dev, v, _, f = _inputs(points, None, faces, _lib.device(device, "point-cloud evaluation"))
+    with torch.cuda.device(dev):
+        out, stats = mesh_sample.sample_device(v, None, f, dev, density)
+    return out["xyz"], dict(stats, spacing=float(spacing))
+
+
 class NearestPlan:
     """Capped nearest neighbours of every query point in the target (device float32 (n,3) tensors or numpy arrays).  The
     constructor uploads, picks the grid and allocates (it may synchronise); ``enqueue()`` only launches, on torch's current
@@ -384,10 +409,12 @@ class EvaluationPlan:
     current stream (capturable); ``result()`` synchronises once and returns the metrics dict of evaluate_point_clouds."""
 
     def __init__(self, pred, gt, *, max_dist, thresholds=(), transform=None, crop=None, voxel_pred=0.0, voxel_gt=0.0,
-                 align=None, device=None):
+                 align=None, device=None, pred_faces=None, pred_spacing=None, gt_faces=None, gt_spacing=None):
         import torch
         from . import _lib
         self.max_dist, self.thresholds = check_thresholds(thresholds, max_dist)
+        pred, self.pred_sampling = _surface(pred, pred_faces, pred_spacing, "pred", device)
+        gt, self.gt_sampling = _surface(gt, gt_faces, gt_spacing, "gt", device)
         self.pred_points, self.gt_points = len(pred), len(gt)
         self.alignment = None
         if align is not None:
@@ -450,17 +477,22 @@ class EvaluationPlan:
                     "grid_pred_to_gt": self.acc.grid, "grid_gt_to_pred": self.comp.grid})
         if self.alignment is not None:
             out["alignment"] = self.alignment
+        for name, sampling in (("pred_sampling", self.pred_sampling), ("gt_sampling", self.gt_sampling)):
+            if sampling is not None:
+                out[name] = sampling
         return out
 
 
 def evaluate_point_clouds(pred, gt, *, max_dist, thresholds=(), transform=None, crop=None, voxel_pred=0.0, voxel_gt=0.0,
-                          align=None, device=None):
+                          align=None, device=None, pred_faces=None, pred_spacing=None, gt_faces=None, gt_spacing=None):
     """Accuracy / completeness / precision / recall / F-score of pred against gt (numpy arrays or device tensors (n,3)) on
     the GPU; semantics in the module docstring.  Returns the metrics dict (plus the point counts before and after the
     preprocessing and the two grids that were used).  align: None, or a dict of register_point_clouds options (at least
-    "stages") to refine `transform` by ICP first."""
+    "stages") to refine `transform` by ICP first.  pred_faces / gt_faces (F,3) int32 with pred_spacing / gt_spacing: that side
+    is a mesh with pred / gt its vertices, and its surface samples are evaluated."""
     plan = EvaluationPlan(pred, gt, max_dist=max_dist, thresholds=thresholds, transform=transform, crop=crop,
-                          voxel_pred=voxel_pred, voxel_gt=voxel_gt, align=align, device=device)
+                          voxel_pred=voxel_pred, voxel_gt=voxel_gt, align=align, device=device, pred_faces=pred_faces,
+                          pred_spacing=pred_spacing, gt_faces=gt_faces, gt_spacing=gt_spacing)
     plan.enqueue()
     return plan.result()
 
@@ -489,7 +521,16 @@ def main(argv=None):
     ap.add_argument("--align", default=None, choices=["icp"], help="refine --transform (or identity) by ICP before evaluating")
     ap.add_argument("--align_stages", default=None, help="voxel:max_corr_dist:max_iterations[,...] (mvsnet_amd.register)")
     ap.add_argument("--align_with_scale", action="store_true", help="let the alignment solve for a uniform scale as well")
+    from .mesh_sample import add_options, check_spacing, read_ply_mesh
+    add_options(ap, "pred_")
+    add_options(ap, "gt_")
     a = ap.parse_args(argv)
+    try:
+        for s in (a.pred_spacing, a.gt_spacing):
+            if s is not None:
+                check_spacing(s)
+    except ValueError as e:
+        raise SystemExit("mvsnet_amd.evaluate: --pred_spacing / --gt_spacing: %s" % e)
     align = None
     if a.align:
         from . import register
@@ -508,11 +549,24 @@ def main(argv=None):
     thresholds = _floats(a.thresholds, what="--thresholds")
     crop = _floats(a.crop, 6, "--crop") if a.crop else None
     transform = np.loadtxt(a.transform, dtype=np.float64).reshape(4, 4) if a.transform else None
-    pred, _ = read_ply_points(a.pred)
-    gt, _ = read_ply_points(a.gt)
+    try:
+        pred_faces = gt_faces = None
+        if a.pred_spacing is None:
+            pred, _ = read_ply_points(a.pred)
+        else:
+            pred, _, pred_faces = read_ply_mesh(a.pred)
+        if a.gt_spacing is None:
+            gt, _ = read_ply_points(a.gt)
+        else:
+            gt, _, gt_faces = read_ply_mesh(a.gt)
+    except ValueError as e:
+        if a.pred_spacing is None and a.gt_spacing is None:
+            raise
+        raise SystemExit("mvsnet_amd.evaluate: %s" % e)
     try:
         plan = EvaluationPlan(pred, gt, max_dist=a.max_dist, thresholds=thresholds, transform=transform, crop=crop,
-                              voxel_pred=a.voxel_pred, voxel_gt=a.voxel_gt, align=align)
+                              voxel_pred=a.voxel_pred, voxel_gt=a.voxel_gt, align=align, pred_faces=pred_faces,
+                              pred_spacing=a.pred_spacing, gt_faces=gt_faces, gt_spacing=a.gt_spacing)
     except ValueError as e:
         raise SystemExit("mvsnet_amd.evaluate: %s" % e)
     plan.enqueue()

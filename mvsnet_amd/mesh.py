@@ -4,6 +4,7 @@ mesh by naive surface nets, the last stage between the depth maps and a model th
     python -m mvsnet_amd.mesh --dense_folder DIR [--out mesh.ply] [--voxel S | --resolution R] [--bounds x0:y0:z0:x1:y1:z1]
         [--trunc_voxels 4] [--prob_threshold 0.8] [--num_consistent 3] [--min_count 1] [--fusion_sources all|listed] [--force]
         [--min_component_faces 0] [--min_component_extent 0] [--keep_largest 0] [--simplify_voxels S]
+        [--eval_gt G.ply --eval_spacing s [--eval_max_dist 20] [--eval_thresholds 0.5,1,2]]
 
 The kernels are csrc/tsdf.hip (mvs_tsdf_integrate_f32, mvs_surface_nets_count_f32, mvs_surface_nets_write_f32); torch owns the
 device memory and the two scans between counting and writing.
@@ -54,6 +55,10 @@ nothing of it runs and the mesh is the extraction's, byte for byte.
 Fewer faces: with simplify_voxels = S > 0 (not necessarily an integer) the mesh, after the removal of its small pieces, goes
 through mvsnet_amd.mesh_simplify (its docstring has the semantics) on the device: vertex clustering in cells of
 float32(S voxel), aligned to the volume's origin.  Without it nothing of it runs and the mesh bytes are unchanged.
+
+A score: with eval_gt (a ground-truth cloud, PLY) and eval_spacing = s the mesh, as it is written (after the removal of small
+pieces and the simplification), is evaluated by its surface samples at spacing s (mvsnet_amd.mesh_sample, then
+mvsnet_amd.evaluate) and the metrics go to mesh_metrics.json beside the PLY.  Without them nothing of it runs.
 """
 from __future__ import annotations
 
@@ -427,6 +432,12 @@ def build_parser():
     add_options(ap)
     from .mesh_simplify import add_option
     add_option(ap)
+    ap.add_argument("--eval_gt", default=None, help="ground-truth cloud (PLY): evaluate the mesh's surface samples against it "
+                    "(mesh_metrics.json beside the output; needs --eval_spacing)")
+    from .mesh_sample import add_options as add_sampling
+    add_sampling(ap, "eval_")
+    ap.add_argument("--eval_max_dist", type=float, default=20.0, help="--eval_gt: distance cap (outliers at or beyond it)")
+    ap.add_argument("--eval_thresholds", default="", help="--eval_gt: comma-separated tau for precision / recall / F-score")
     return ap
 
 
@@ -453,6 +464,20 @@ def parse_args(argv=None):
                              "and >= 0 (%s)" % e)
         if a.simplify_voxels is not None and not (a.simplify_voxels > 0 and math.isfinite(a.simplify_voxels)):
             raise ValueError("--simplify_voxels must be positive and finite, got %r" % (a.simplify_voxels,))
+        if (a.eval_gt is None) != (a.eval_spacing is None):
+            raise ValueError("--eval_gt and --eval_spacing go together")
+        try:
+            a.eval_thresholds = [float(v) for v in a.eval_thresholds.split(",") if v.strip()]
+        except ValueError:
+            raise ValueError("--eval_thresholds: comma-separated numbers expected, got %r" % (a.eval_thresholds,))
+        if a.eval_gt is not None:
+            from .evaluate import check_thresholds
+            from .mesh_sample import check_spacing
+            try:
+                check_spacing(a.eval_spacing)
+                check_thresholds(a.eval_thresholds, a.eval_max_dist)
+            except ValueError as e:
+                raise ValueError("--eval_spacing / --eval_max_dist / --eval_thresholds: %s" % e)
     except ValueError as e:
         raise SystemExit("mvsnet_amd.mesh: %s" % e)
     if a.out is None:
@@ -467,9 +492,30 @@ def prepare_output(a):
     return a.out
 
 
-def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", **options):
-    """The dense folder's depth maps -> the PLY at `out`; returns the report the command line prints."""
+def evaluate_mesh(out, vertices, faces, eval_gt, eval_spacing, eval_max_dist=20.0, eval_thresholds=()):
+    """The mesh against the ground-truth cloud eval_gt (a PLY) by its surface samples at eval_spacing -> the metrics, also
+    written to mesh_metrics.json beside `out`."""
+    from . import evaluate
+    gt, _ = evaluate.read_ply_points(eval_gt)
+    metrics = evaluate.evaluate_point_clouds(vertices, gt, max_dist=eval_max_dist, thresholds=eval_thresholds, pred_faces=faces,
+                                             pred_spacing=eval_spacing)
+    with open(os.path.join(os.path.dirname(os.path.abspath(out)), "mesh_metrics.json"), "w") as f:
+        f.write(json.dumps(metrics) + "\n")
+    return metrics
+
+
+def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", eval_gt=None, eval_spacing=None, eval_max_dist=20.0,
+                      eval_thresholds=(), **options):
+    """The dense folder's depth maps -> the PLY at `out`; returns the report the command line prints.  With eval_gt and
+    eval_spacing also mesh_metrics.json beside it (evaluate_mesh); the report then names it."""
     from . import fusion
+    if (eval_gt is None) != (eval_spacing is None):
+        raise ValueError("eval_gt and eval_spacing go together")
+    if eval_gt is not None:                                                    # before any GPU work
+        from .evaluate import check_thresholds
+        from .mesh_sample import check_spacing
+        check_spacing(eval_spacing)
+        check_thresholds(eval_thresholds, eval_max_dist)
     indices, depths, probs, cams, images = fusion.load_dense_folder(dense_folder)
     sources = fusion.listed_sources(dense_folder, indices) if fusion_sources == "listed" else None
     vertices, colours, faces, cleaned = _mesh_depth_maps(depths, probs, cams, images, sources=sources, **options)
@@ -478,6 +524,9 @@ def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", **options):
     report = {"views": len(indices), "vertices": int(len(vertices)), "faces": int(len(faces)), "out": out}
     if cleaned is not None:
         report.update(cleaned)                                                 # the cleaning's fields (mesh_clean.py, Report)
+    if eval_gt is not None:
+        evaluate_mesh(out, vertices, faces, eval_gt, eval_spacing, eval_max_dist, eval_thresholds)
+        report["mesh_metrics"] = os.path.join(os.path.dirname(os.path.abspath(out)), "mesh_metrics.json")
     return report
 
 
@@ -493,7 +542,9 @@ def main(argv=None):
                                    bounds=a.bounds, trunc_voxels=a.trunc_voxels, num_consistent=a.num_consistent,
                                    prob_threshold=a.prob_threshold, min_count=a.min_count,
                                    min_component_faces=a.min_component_faces, min_component_extent=a.min_component_extent,
-                                   keep_largest=a.keep_largest, simplify_voxels=a.simplify_voxels)
+                                   keep_largest=a.keep_largest, simplify_voxels=a.simplify_voxels,
+                                   **({} if a.eval_gt is None else dict(eval_gt=a.eval_gt, eval_spacing=a.eval_spacing,
+                                                                        eval_max_dist=a.eval_max_dist, eval_thresholds=a.eval_thresholds)))
     except (ValueError, OSError) as e:
         raise SystemExit("mvsnet_amd.mesh: %s" % e)
     print(json.dumps(report))
