@@ -980,6 +980,44 @@ int mvs_mesh_sample_write_f32(const float* vertices, const unsigned char* colour
                               const long long* sums, long long N, unsigned long long seed, float* out_xyz, int* out_face,
                               unsigned char* out_colours, float* out_normals, void* stream);
 
+/* Taubin smoothing of a triangle mesh: Jacobi passes over a sorted adjacency structure (csrc/mesh_smooth.hip; semantics in
+ * mvsnet_amd/mesh_smooth.py).  M vertices, 0..2^31-1, and F faces with 6 F <= 2^31-1 (negative: MVS_E_BADARG, beyond:
+ * MVS_E_SHAPE); E = 6 F.  A pointer to an array of M, F or E entries may be NULL when that size is 0.  The caller sorts and
+ * scans between the calls:
+ *   mvs_mesh_smooth_edges_i64   vertices (M,3) float32, faces (F,3) int32 -> keys (E) int64: per face the directed edges a>b b>a
+ *                 b>c c>b c>a a>c as int64(s) << 31 | t; INT64_MAX for an edge with s == t or an end that is not finite, and for
+ *                 all six of a face with an index outside 0..M-1.  Clears the status words; counts words 0 and 1
+ *   (an ascending sort of keys -> sorted_keys (E) int64)
+ *   mvs_mesh_smooth_heads_i64   -> head (E) int32: 1 where a run of equal live keys starts, else 0.  Counts words 2 and 3
+ *   (an inclusive scan of head -> head_rank (E) int32; its last entry is the number of unique directed edges U)
+ *   mvs_mesh_smooth_rows_i32    boundary 0 fixed, 1 curve, 2 free (else MVS_E_BADARG) -> neighbours (E) int32: entries 0..U-1
+ *                 are written, the target in bits 0..30 and bit 31 set on a boundary edge, the rest is left alone; row_start
+ *                 (M + 1) int32: the unique edges whose source is below v; vertex_class (M) uint8: 0 fixed, 1 curve, 2 interior.
+ *                 Counts words 4 and 5
+ *   mvs_mesh_smooth_step_f32    one pass X -> Y (never the same array: MVS_E_BADARG) with the float32 factor (finite) over the
+ *                 rows; V0 the positions the bound is taken from, max_displacement r >= 0 or negative for none (NaN, +inf:
+ *                 MVS_E_BADARG); N the entries of neighbours, 0..2^31-1, against which the row bounds are checked.  X, V0 and Y
+ *                 are (M, row_floats) float32 with row_floats 3, or 4 with 16-byte aligned arrays, where the fourth float
+ *                 travels from X to Y as it is
+ *   workspace     mvs_mesh_smooth_workspace_bytes(M, F) bytes (0 for invalid sizes): 64 int32 status words (0 invalid faces,
+ *                 1 vertices that are not finite, 2 boundary edges, 3 non-manifold edges, 4 boundary vertices, 5 fixed vertices);
+ *                 each call clears the words it counts
+ * All four only enqueue on `stream`: nothing is allocated, nothing synchronised.  The only atomics are integer counts, and the
+ * sums of a pass run in one order, so the same inputs give the same bytes on any grid.  Every argument is checked before the
+ * first GPU call and the outputs are untouched on error.  Every index read from an array (faces, head_rank, row_start,
+ * neighbours) is range-checked before it is used. */
+size_t mvs_mesh_smooth_workspace_bytes(long long M, long long F);
+int mvs_mesh_smooth_edges_i64(const float* vertices, long long M, const int* faces, long long F, long long* keys, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int mvs_mesh_smooth_heads_i64(const long long* sorted_keys, long long F, int* head, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int mvs_mesh_smooth_rows_i32(const long long* sorted_keys, const int* head, const int* head_rank, long long M, long long F,
+                             int boundary, int* neighbours, int* row_start, unsigned char* vertex_class, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int mvs_mesh_smooth_step_f32(const float* X, const float* V0, const int* row_start, const int* neighbours,
+                             const unsigned char* vertex_class, long long M, long long N, int row_floats, float factor,
+                             float max_displacement, float* Y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,13 @@ SIGNATURES = {
     "mvs_mesh_sample_workspace_bytes": (_sz, [_ll, _ll]),
     "mvs_mesh_sample_quota_f32": (_i, [_p, _ll, _p, _ll, C.c_double, _p, _p, _sz, _p]),
     "mvs_mesh_sample_write_f32": (_i, [_p, _p, _ll, _p, _ll, _p, _ll, C.c_ulonglong, _p, _p, _p, _p, _p]),
+    # Taubin smoothing (csrc/mesh_smooth.hip; the header has it last), before mvs_fusion_workspace_bytes for the same reason; its
+    # arena cases and pin are tests/test_gpu_arena_mesh_smooth.py
+    "mvs_mesh_smooth_workspace_bytes": (_sz, [_ll, _ll]),
+    "mvs_mesh_smooth_edges_i64": (_i, [_p, _ll, _p, _ll, _p, _p, _sz, _p]),
+    "mvs_mesh_smooth_heads_i64": (_i, [_p, _ll, _p, _p, _sz, _p]),
+    "mvs_mesh_smooth_rows_i32": (_i, [_p, _p, _p, _ll, _ll, _i, _p, _p, _p, _p, _sz, _p]),
+    "mvs_mesh_smooth_step_f32": (_i, [_p, _p, _p, _p, _p, _ll, _ll, _i, _f, _f, _p, _p]),
     "mvs_fusion_workspace_bytes": (_sz, [_i] * 5),
     "mvs_fusion_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "mvs_depth_normals_f32": (_i, [_p, _p, _i, _i, _i, _p, _f, _f, _p, _p]),

@@ -16,6 +16,8 @@ points_mvsnet/consistencyCheck-<YYYYmmdd-HHMMSS>/final3d_model.ply, the path the
     python -m mvsnet_amd.depthfusion --dense_folder <dir> --fusion hip [--reproj_threshold 1.0]
         [--depth_rel_threshold 0.01] [--no_dedupe] [--fusion_sources {all,listed}] [--mesh]
         [--mesh_min_component_faces 0] [--mesh_min_component_extent 0] [--mesh_keep_largest 0] [--mesh_simplify_voxels S]
+        [--mesh_smooth_iterations N [--mesh_smooth_lambda 0.5] [--mesh_smooth_mu -0.53] [--mesh_smooth_boundary fixed|curve|free]
+         [--mesh_smooth_max_voxels 1]]
         [--eval_gt G.ply [--eval_max_dist 20] [--eval_thresholds 0.5,1,2] [--mesh_eval_spacing s]]
         [--normals] [--normal_angle_threshold DEG] [--jump_threshold 0.05] [--write_normal_maps]
 --normals estimates surface normals from the depth maps on the GPU and writes the PLY as x y z nx ny nz red green blue
@@ -140,14 +142,15 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
 def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent,
                dedupe=True, fusion_sources="all", eval_gt=None, eval_max_dist=20.0, eval_thresholds=(), normals=False,
                normal_angle_threshold=None, jump_threshold=0.05, write_normal_maps=False, mesh=False, mesh_clean=None,
-               mesh_simplify_voxels=None, mesh_eval_spacing=None):
+               mesh_simplify_voxels=None, mesh_eval_spacing=None, mesh_smooth=None):
     """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply
     (with normals: x y z nx ny nz red green blue; write_normal_maps: depths_mvsnet/<idx>_normal.pfm, camera frame).
     With eval_gt (a PLY), the fused cloud is evaluated against it on the device (mvsnet_amd.evaluate) and the metrics are
     written to metrics.json next to the PLY.  With mesh, mvsnet_amd.mesh writes mesh.ply beside it: TSDF fusion and surface
     nets of the same depth maps under the same consistency criteria; mesh_clean = dict(min_component_faces=,
     min_component_extent=, keep_largest=) removes its small pieces (mvsnet_amd.mesh_clean) and mesh_simplify_voxels = S clusters
-    its vertices in cells of S voxels (mvsnet_amd.mesh_simplify).  With mesh, eval_gt and mesh_eval_spacing = s the mesh, as it
+    its vertices in cells of S voxels (mvsnet_amd.mesh_simplify); mesh_smooth = dict(iterations=, lam=, mu=, boundary=,
+    max_voxels=) smooths it in between (mvsnet_amd.mesh_smooth).  With mesh, eval_gt and mesh_eval_spacing = s the mesh, as it
     is written, is evaluated against the same ground truth by its surface samples at spacing s (mvsnet_amd.mesh_sample) into
     mesh_metrics.json beside mesh.ply; metrics.json stays the cloud's."""
     import json
@@ -180,11 +183,11 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
             f.write(json.dumps(metrics) + "\n")
         print("evaluated against %s: %s" % (eval_gt, json.dumps(metrics)))
     if mesh:
-        from .mesh import mesh_dense_folder
+        from .mesh import mesh_dense_folder, smooth_options
         print("meshed: %s" % json.dumps(mesh_dense_folder(
             dense_folder, os.path.join(out, "mesh.ply"), fusion_sources=fusion_sources, prob_threshold=prob_threshold,
             reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent,
-            simplify_voxels=mesh_simplify_voxels, **dict(
+            simplify_voxels=mesh_simplify_voxels, **smooth_options(mesh_smooth), **dict(
                 mesh_clean or {}, **({} if mesh_eval_spacing is None else dict(
                     eval_gt=eval_gt, eval_spacing=mesh_eval_spacing, eval_max_dist=eval_max_dist, eval_thresholds=eval_thresholds))))))
     return path
@@ -228,7 +231,16 @@ def main(argv=None):
     add_option(ap, "mesh_")
     from .mesh_sample import add_options as add_sampling, check_spacing
     add_sampling(ap, "mesh_eval_")
+    from .mesh_smooth import add_options as add_smoothing, check_smooth_arguments
+    add_smoothing(ap, "mesh_")
     a = ap.parse_args(argv)
+    for name in ("iterations", "lambda", "mu", "boundary", "max_voxels"):
+        if getattr(a, "mesh_smooth_" + name) != ap.get_default("mesh_smooth_" + name) and not a.mesh:
+            raise SystemExit("--mesh_smooth_%s needs --mesh" % name)
+    try:
+        mesh_smooth = check_smooth_arguments(a, "mesh_")
+    except ValueError as e:
+        raise SystemExit(str(e))
     if a.mesh_eval_spacing is not None:
         if not (a.mesh and a.eval_gt):
             raise SystemExit("--mesh_eval_spacing needs --mesh and --eval_gt")
@@ -289,7 +301,7 @@ def main(argv=None):
                           jump_threshold=0.05 if a.jump_threshold is None else a.jump_threshold,
                           write_normal_maps=a.write_normal_maps, mesh=a.mesh,
                           mesh_clean=dict(min_component_faces=clean[0], min_component_extent=clean[1], keep_largest=clean[2]),
-                          mesh_simplify_voxels=a.mesh_simplify_voxels, mesh_eval_spacing=a.mesh_eval_spacing)
+                          mesh_simplify_voxels=a.mesh_simplify_voxels, mesh_eval_spacing=a.mesh_eval_spacing, mesh_smooth=mesh_smooth)
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")

@@ -4,6 +4,7 @@ mesh by naive surface nets, the last stage between the depth maps and a model th
     python -m mvsnet_amd.mesh --dense_folder DIR [--out mesh.ply] [--voxel S | --resolution R] [--bounds x0:y0:z0:x1:y1:z1]
         [--trunc_voxels 4] [--prob_threshold 0.8] [--num_consistent 3] [--min_count 1] [--fusion_sources all|listed] [--force]
         [--min_component_faces 0] [--min_component_extent 0] [--keep_largest 0] [--simplify_voxels S]
+        [--smooth_iterations N [--smooth_lambda 0.5] [--smooth_mu -0.53] [--smooth_boundary fixed|curve|free] [--smooth_max_voxels 1]]
         [--eval_gt G.ply --eval_spacing s [--eval_max_dist 20] [--eval_thresholds 0.5,1,2]]
 
 The kernels are csrc/tsdf.hip (mvs_tsdf_integrate_f32, mvs_surface_nets_count_f32, mvs_surface_nets_write_f32); torch owns the
@@ -52,12 +53,17 @@ Small pieces: with min_component_faces, min_component_extent or keep_largest non
 mvsnet_amd.mesh_clean (its docstring has the semantics) on the device, before the copy to the host; with all three at 0
 nothing of it runs and the mesh is the extraction's, byte for byte.
 
+Less noise: with smooth_iterations = N > 0 the mesh, after the removal of its small pieces and before any simplification, goes
+through mvsnet_amd.mesh_smooth (its docstring has the semantics) on the device: N Taubin iterations with smooth_lambda and
+smooth_mu, boundary vertices treated as smooth_boundary says, and no coordinate farther than float32(smooth_max_voxels voxel)
+from where the extraction put it.  With 0 nothing of it runs and the mesh bytes are unchanged.
+
 Fewer faces: with simplify_voxels = S > 0 (not necessarily an integer) the mesh, after the removal of its small pieces, goes
 through mvsnet_amd.mesh_simplify (its docstring has the semantics) on the device: vertex clustering in cells of
 float32(S voxel), aligned to the volume's origin.  Without it nothing of it runs and the mesh bytes are unchanged.
 
 A score: with eval_gt (a ground-truth cloud, PLY) and eval_spacing = s the mesh, as it is written (after the removal of small
-pieces and the simplification), is evaluated by its surface samples at spacing s (mvsnet_amd.mesh_sample, then
+pieces, the smoothing and the simplification), is evaluated by its surface samples at spacing s (mvsnet_amd.mesh_sample, then
 mvsnet_amd.evaluate) and the metrics go to mesh_metrics.json beside the PLY.  Without them nothing of it runs.
 """
 from __future__ import annotations
@@ -275,12 +281,14 @@ class TsdfVolume:
             _lib.check(rc, "mvs_tsdf_integrate_f32")
         return self
 
-    def extract(self, min_count=1, clean=None, simplify=None):
+    def extract(self, min_count=1, clean=None, simplify=None, smooth=None):
         """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation.  With
         clean = dict(min_faces=, min_extent=, keep_largest=) the mesh goes through mesh_clean.clean_mesh on the device before
         the copy to the host and the result is (vertices, colours, faces, report).  With simplify = cell (world units) it then
         goes through mesh_simplify.simplify_device with cells aligned to the volume's origin; the result is (vertices, colours,
-        faces, report) with the simplification's report under "simplify", beside the cleaning's fields if there are any."""
+        faces, report) with the simplification's report under "simplify", beside the cleaning's fields if there are any.  With
+        smooth = dict(iterations=, lam=, mu=, boundary=, max_displacement=) (mesh_smooth.check_options) the mesh goes through
+        mesh_smooth.smooth_device after the cleaning and before the simplification; its report goes under "smooth"."""
         import torch
         from . import _lib
         min_count = check_min_count(min_count)
@@ -290,6 +298,9 @@ class TsdfVolume:
         if simplify is not None:
             from . import mesh_simplify
             simplify = mesh_simplify.check_cell(simplify)
+        if smooth is not None:
+            from . import mesh_smooth
+            smooth = mesh_smooth.check_options(**smooth)
         lib = _lib.load()
         nx, ny, nz = self.dims
         nodes = nx * ny * nz
@@ -320,6 +331,9 @@ class TsdfVolume:
             report = None
             if clean is not None:
                 vertices, colours, faces, report = mesh_clean.clean_device(vertices, colours, faces, self.dev, *clean)
+            if smooth is not None:
+                vertices, colours, faces, smoothed = mesh_smooth.smooth_device(vertices, colours, faces, self.dev, *smooth)
+                report = dict(report or {}, smooth=smoothed)
             if simplify is not None:
                 vertices, colours, faces, simplified = mesh_simplify.simplify_device(vertices, colours, faces, self.dev, simplify,
                                                                                      self.origin)
@@ -364,17 +378,24 @@ def mesh_depth_maps(depths, probs, cams, images=None, **options):
     along the longest axis, 256 when neither is given); bounds (lo, hi) default to the box of the consistent points.  Options:
     voxel, resolution, bounds, trunc_voxels, num_consistent, prob_threshold, reproj_threshold, depth_rel_threshold, sources,
     min_count, device, min_component_faces, min_component_extent, keep_largest (all 0: no cleaning runs), and simplify_voxels
-    (None or 0: no simplification runs; S > 0: vertex clustering in cells of float32(S voxel))."""
+    (None or 0: no simplification runs; S > 0: vertex clustering in cells of float32(S voxel)), and smooth_iterations (0: no
+    smoothing runs) with smooth_lambda, smooth_mu, smooth_boundary and smooth_max_voxels (the bound is float32(R voxel))."""
     return _mesh_depth_maps(depths, probs, cams, images, **options)[:3]
 
 
 def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution=None, bounds=None, trunc_voxels=4,
                      num_consistent=3, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, sources=None,
                      min_count=1, device=None, min_component_faces=0, min_component_extent=0.0, keep_largest=0,
-                     simplify_voxels=None):
-    """mesh_depth_maps -> (vertices, colours, faces, the report of the cleaning and the simplification or None)."""
-    from . import mesh_clean, mesh_simplify
+                     simplify_voxels=None, smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed",
+                     smooth_max_voxels=1.0):
+    """mesh_depth_maps -> (vertices, colours, faces, the report of the cleaning, the smoothing and the simplification or None)."""
+    from . import mesh_clean, mesh_simplify, mesh_smooth
     simplify_voxels = mesh_simplify.check_voxels(simplify_voxels)
+    smooth_iterations = mesh_smooth.check_iterations(smooth_iterations, least=0)
+    smooth = None
+    if smooth_iterations:
+        smooth_max_voxels = mesh_smooth.check_voxels(smooth_max_voxels)
+        mesh_smooth.check_options(smooth_iterations, smooth_lambda, smooth_mu, smooth_boundary)      # before any GPU work
     from .fusion import FusionPlan
     clean = mesh_clean.check_options(min_component_faces, min_component_extent, keep_largest)
     clean = dict(zip(mesh_clean.OPTION_NAMES, clean)) if mesh_clean.wanted(*clean) else None
@@ -405,10 +426,13 @@ def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution
         origin, voxel, dims = choose_volume(bounds[0], bounds[1], voxel, resolution)
     vol = TsdfVolume(origin, voxel, dims, tv * voxel, colour=images is not None, device=device)
     vol.integrate(depths, probs, cams, images, prob_threshold=prob_threshold)
-    if clean is None and simplify_voxels is None:
+    if clean is None and simplify_voxels is None and not smooth_iterations:
         return vol.extract(min_count) + (None,)
     cell = None if simplify_voxels is None else float(np.float32(simplify_voxels * vol.voxel))
-    return vol.extract(min_count, clean=clean, simplify=cell)
+    if smooth_iterations:
+        smooth = dict(iterations=smooth_iterations, lam=smooth_lambda, mu=smooth_mu, boundary=smooth_boundary,
+                      max_displacement=float(np.float32(smooth_max_voxels * vol.voxel)))
+    return vol.extract(min_count, clean=clean, simplify=cell, smooth=smooth)
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -432,6 +456,8 @@ def build_parser():
     add_options(ap)
     from .mesh_simplify import add_option
     add_option(ap)
+    from .mesh_smooth import add_options as add_smoothing
+    add_smoothing(ap)
     ap.add_argument("--eval_gt", default=None, help="ground-truth cloud (PLY): evaluate the mesh's surface samples against it "
                     "(mesh_metrics.json beside the output; needs --eval_spacing)")
     from .mesh_sample import add_options as add_sampling
@@ -464,6 +490,8 @@ def parse_args(argv=None):
                              "and >= 0 (%s)" % e)
         if a.simplify_voxels is not None and not (a.simplify_voxels > 0 and math.isfinite(a.simplify_voxels)):
             raise ValueError("--simplify_voxels must be positive and finite, got %r" % (a.simplify_voxels,))
+        from .mesh_smooth import check_smooth_arguments
+        a.smooth = check_smooth_arguments(a)                                   # None: --smooth_iterations 0, nothing of it runs
         if (a.eval_gt is None) != (a.eval_spacing is None):
             raise ValueError("--eval_gt and --eval_spacing go together")
         try:
@@ -530,6 +558,14 @@ def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", eval_gt=None, 
     return report
 
 
+def smooth_options(smooth):
+    """check_smooth_arguments' dict (or None) -> the smooth_* options of mesh_depth_maps and mesh_dense_folder."""
+    if smooth is None:
+        return {}
+    return dict(smooth_iterations=smooth["iterations"], smooth_lambda=smooth["lam"], smooth_mu=smooth["mu"],
+                smooth_boundary=smooth["boundary"], smooth_max_voxels=smooth["max_voxels"])
+
+
 def main(argv=None):
     a = parse_args(argv)
     out = prepare_output(a)
@@ -542,7 +578,7 @@ def main(argv=None):
                                    bounds=a.bounds, trunc_voxels=a.trunc_voxels, num_consistent=a.num_consistent,
                                    prob_threshold=a.prob_threshold, min_count=a.min_count,
                                    min_component_faces=a.min_component_faces, min_component_extent=a.min_component_extent,
-                                   keep_largest=a.keep_largest, simplify_voxels=a.simplify_voxels,
+                                   keep_largest=a.keep_largest, simplify_voxels=a.simplify_voxels, **smooth_options(a.smooth),
                                    **({} if a.eval_gt is None else dict(eval_gt=a.eval_gt, eval_spacing=a.eval_spacing,
                                                                         eval_max_dist=a.eval_max_dist, eval_thresholds=a.eval_thresholds)))
     except (ValueError, OSError) as e:
