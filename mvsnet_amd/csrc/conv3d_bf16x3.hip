@@ -146,7 +146,7 @@ conv3d_s1_bf16_kernel(ConvArgs a) {
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int v = 0; v < V; ++v) acc[m][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
+    double st_s[4] = {0.0, 0.0, 0.0, 0.0}, st_q[4] = {0.0, 0.0, 0.0, 0.0};      // doubles: E[x^2] - E[x]^2 multiplies a float32 run's rounding by (mean / deviation)^2
 
     int b_off[V];                                  // byte offsets
 #pragma unroll
@@ -216,7 +216,7 @@ conv3d_s1_bf16_kernel(ConvArgs a) {
                     float* dst = a.y + ((((size_t)o * a.H + h) * a.W) + w) * a.cout_total + co_base + co;
                     *(float4*)dst = make_float4(r[0], r[1], r[2], r[3]);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) { st_s[k] += r[k]; st_q[k] += r[k] * r[k]; }
+                    for (int k = 0; k < 4; ++k) { const double v = (double)r[k]; st_s[k] += v; st_q[k] = fma(v, v, st_q[k]); }
                 }
                 acc[mt][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }

@@ -184,7 +184,7 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
     f32x4 acc[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
+    double st_s[4] = {0.0, 0.0, 0.0, 0.0}, st_q[4] = {0.0, 0.0, 0.0, 0.0};      // doubles: E[x^2] - E[x]^2 multiplies a float32 run's rounding by (mean / deviation)^2
 
     // B operand: staged row 2*wave + i (i = 0..3, an immediate), column n + kw, slot kq (s = 1 is ^16)
     int bcol[3];
@@ -266,7 +266,7 @@ conv3d_c8_kernel(ConvArgs a, FuseArgs fa) {
                 __builtin_amdgcn_raw_buffer_store_b128(v, yrsrc, yo + o * yplane_bytes, 0, 0);
                 if (yo >= 0) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) { st_s[k] += r[k]; st_q[k] += r[k] * r[k]; }
+                    for (int k = 0; k < 4; ++k) { const double v = (double)r[k]; st_s[k] += v; st_q[k] = fma(v, v, st_q[k]); }
                 }
             }
             r = (f32x4){0.f, 0.f, 0.f, 0.f};

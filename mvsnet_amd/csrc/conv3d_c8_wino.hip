@@ -196,7 +196,7 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
     for (int p = 0; p < NPT; ++p)
 #pragma unroll
         for (int i = 0; i < 3; ++i) acc[p][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
+    double st_s[4] = {0.0, 0.0, 0.0, 0.0}, st_q[4] = {0.0, 0.0, 0.0, 0.0};      // doubles: E[x^2] - E[x]^2 multiplies a float32 run's rounding by (mean / deviation)^2
 
     // raw operand d_c: staged row 2*rw + i (i = 0..3, an immediate), column 2n + c, slot kq (s = 1 is ^16)
     int bcol[4];
@@ -299,7 +299,7 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
                     __builtin_amdgcn_raw_buffer_store_b128(v, yrsrc, yo + e * COUT * 4 + o * yplane_bytes, 0, 0);
                     if (yo >= 0) {
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) { st_s[k] += y[e][k]; st_q[k] = __builtin_fmaf(y[e][k], y[e][k], st_q[k]); }
+                        for (int k = 0; k < 4; ++k) { const double v = (double)y[e][k]; st_s[k] += v; st_q[k] = fma(v, v, st_q[k]); }
                     }
                 }
             }
@@ -320,7 +320,7 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
     float wS[3][9][2];
     f32x4 cur[NCT], prv[NCT];                      // output planes od_cur / od_cur - 1, per column tile
     int s2b[3][2];
-    float st2_s[4] = {0.f, 0.f, 0.f, 0.f}, st2_q[4] = {0.f, 0.f, 0.f, 0.f};
+    double st2_s[4] = {0.0, 0.0, 0.0, 0.0}, st2_q[4] = {0.0, 0.0, 0.0, 0.0};
     int fin_od = -1;                               // output plane whose partial tiles wait in `red`
     const int Ho = a.H / 2, Wo = a.W / 2;
     auto init_s2 = [&]() __attribute__((always_inline)) {
@@ -398,7 +398,7 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
                     float* dst = fa.y2 + ((((size_t)fin_od * Ho + oh) * Wo) + ow) * COUT2 + 4 * kq;
                     *(float4*)dst = make_float4(r[0], r[1], r[2], r[3]);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) { st2_s[k] += r[k]; st2_q[k] = __builtin_fmaf(r[k], r[k], st2_q[k]); }
+                    for (int k = 0; k < 4; ++k) { const double v = (double)r[k]; st2_s[k] += v; st2_q[k] = fma(v, v, st2_q[k]); }
                 }
             }
         }
@@ -572,13 +572,13 @@ conv3d_c8_wino_kernel(ConvArgs a, WinoArgs fa) {
             if (fa.stats2 && rw == 0) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    float sv = st2_s[k], qv = st2_q[k];
+                    double sv = st2_s[k], qv = st2_q[k];
 #pragma unroll
                     for (int o = 8; o > 0; o >>= 1) { sv += __shfl_xor(sv, o, 64); qv += __shfl_xor(qv, o, 64); }
                     if (n == 0) {
                         double* s2p = fa.stats2 + (size_t)((blockIdx.x + gridDim.x * blockIdx.z) % fa.slots2) * 2 * COUT2;
-                        atomicAdd(&s2p[4 * kq + k], (double)sv);
-                        atomicAdd(&s2p[COUT2 + 4 * kq + k], (double)qv);
+                        atomicAdd(&s2p[4 * kq + k], sv);
+                        atomicAdd(&s2p[COUT2 + 4 * kq + k], qv);
                     }
                 }
             }

@@ -197,7 +197,7 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int v = 0; v < V; ++v) acc[m][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
+    double st_s[4] = {0.0, 0.0, 0.0, 0.0}, st_q[4] = {0.0, 0.0, 0.0, 0.0};      // doubles: E[x^2] - E[x]^2 multiplies a float32 run's rounding by (mean / deviation)^2
 
     // lane constants: B-operand base (floats) per voxel tile, A-operand row decomposition
     int b_off[V];
@@ -271,7 +271,7 @@ conv3d_s1_kernel(ConvArgs a, Fuse2Args fa) {
                     __builtin_amdgcn_raw_buffer_store_b128(u, yrsrc, yoff[v] + co * 4, o * yplane_bytes, 0);
                     if (yoff[v] >= 0) {
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) { st_s[k] += r[k]; st_q[k] += r[k] * r[k]; }
+                        for (int k = 0; k < 4; ++k) { const double v = (double)r[k]; st_s[k] += v; st_q[k] = fma(v, v, st_q[k]); }
                     }
                 }
                 acc[mt][v] = (f32x4){0.f, 0.f, 0.f, 0.f};

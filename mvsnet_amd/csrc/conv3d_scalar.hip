@@ -26,22 +26,24 @@ __device__ __forceinline__ float load_in(const InXform& in, size_t off, int c) {
 
 constexpr int CO_CHUNK = 16;
 
-// Block-level reduction of per-thread channel sums into the float64 accumulators.
+// Block-level reduction of per-thread channel sums into the float64 accumulators.  The fold across the wave is in double too: a
+// float32 fold of 64 lanes costs six roundings of the running sum, which E[x^2] - E[x]^2 multiplies by (mean / deviation)^2
+// (tests/test_gpu_value_conditioning.py: 6 E on the BatchNorm output of an input with a common offset).
 __device__ __forceinline__ void stats_accumulate(const float (&acc)[CO_CHUNK], bool valid, int co0,
                                                  int Cout, double* stats) {
-    __shared__ float red[4][2][CO_CHUNK];
+    __shared__ double red[4][2][CO_CHUNK];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int j = 0; j < CO_CHUNK; ++j) {
-        float v = valid ? acc[j] : 0.f;
-        float s = wave_sum(v), q = wave_sum(v * v);
+        const double v = valid ? (double)acc[j] : 0.0;
+        const double s = wave_sum(v), q = wave_sum(v * v);
         if (lane == 0) { red[wv][0][j] = s; red[wv][1][j] = q; }
     }
     __syncthreads();
     if (threadIdx.x < 2 * CO_CHUNK) {
         int k = threadIdx.x / CO_CHUNK, j = threadIdx.x % CO_CHUNK;
         if (co0 + j < Cout) {
-            double t = (double)red[0][k][j] + (double)red[1][k][j] + (double)red[2][k][j] + (double)red[3][k][j];
+            double t = red[0][k][j] + red[1][k][j] + red[2][k][j] + red[3][k][j];
             atomicAdd(&stats[(size_t)k * Cout + co0 + j], t);
         }
     }

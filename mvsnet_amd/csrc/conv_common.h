@@ -129,18 +129,20 @@ __device__ __forceinline__ float4 bn_relu4(float4 v, float4 s, float4 b, bool af
 
 // Final reduction of per-lane BatchNorm partial sums.  Lane (kq = lane>>4, n = lane&15) holds the
 // sums of channels 4*cq .. 4*cq+3 (cq = channel-quad index given by the caller) over its voxels.
-// `red` is >= 4*2*16 floats of LDS that is dead by now; one f64 atomic per channel per workgroup.
+// `red` is >= 8*2*16 doubles (2 KB, 8-byte aligned) of LDS that is dead by now -- every caller passes its staging slab after the
+// march's last barrier; one f64 atomic per channel per workgroup.  Partials, fold and rows are doubles: E[x^2] - E[x]^2 multiplies
+// a float32 sum's rounding by (mean / deviation)^2 (EXPERIMENTS.md, value-conditioning addendum).
 template <int COUT>
-__device__ __forceinline__ void stats_commit(const float (&st_s)[4], const float (&st_q)[4],
+__device__ __forceinline__ void stats_commit(const double (&st_s)[4], const double (&st_q)[4],
                                              bool fold32, float* red_raw, double* stats,
                                              int cout_total, int co_base) {
-    float (*red)[2][16] = reinterpret_cast<float (*)[2][16]>(red_raw);
+    double (*red)[2][16] = reinterpret_cast<double (*)[2][16]>(red_raw);      // 8-byte aligned: every caller passes its slab
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 15, kq = lane >> 4;
-    float s[4], q[4];
+    double s[4], q[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        float sv = st_s[k], qv = st_q[k];
+        double sv = st_s[k], qv = st_q[k];
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) { sv += __shfl_xor(sv, o, 64); qv += __shfl_xor(qv, o, 64); }
         if (fold32) { sv += __shfl_xor(sv, 32, 64); qv += __shfl_xor(qv, 32, 64); }
@@ -154,7 +156,7 @@ __device__ __forceinline__ void stats_commit(const float (&st_s)[4], const float
     __syncthreads();
     if (tid < 2 * COUT) {
         int k = tid / COUT, c = tid - k * COUT;
-        double t = (double)red[0][k][c] + (double)red[1][k][c] + (double)red[2][k][c] + (double)red[3][k][c];
+        double t = red[0][k][c] + red[1][k][c] + red[2][k][c] + red[3][k][c];
         atomicAdd(&stats[(size_t)k * cout_total + co_base + c], t);
     }
 }

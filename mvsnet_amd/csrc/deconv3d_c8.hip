@@ -158,7 +158,7 @@ deconv3d_c8_kernel(ConvArgs a) {
     for (int t = 0; t < 6; ++t)
 #pragma unroll
         for (int v = 0; v < V; ++v) acc[t][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
+    double st_s[4] = {0.0, 0.0, 0.0, 0.0}, st_q[4] = {0.0, 0.0, 0.0, 0.0};      // doubles: E[x^2] - E[x]^2 multiplies a float32 run's rounding by (mean / deviation)^2
 
     int b_off[V];
 #pragma unroll
@@ -230,7 +230,7 @@ deconv3d_c8_kernel(ConvArgs a) {
                 __builtin_amdgcn_raw_buffer_store_b128(u, yrsrc, yoff[c][v] + od * yplane_bytes, 0, 0);
                 if (yoff[c][v] >= 0) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) { st_s[k] += r[k]; st_q[k] += r[k] * r[k]; }
+                    for (int k = 0; k < 4; ++k) { const double v = (double)r[k]; st_s[k] += v; st_q[k] = fma(v, v, st_q[k]); }
                 }
             }
         }
