@@ -1018,6 +1018,45 @@ int mvs_mesh_smooth_step_f32(const float* X, const float* V0, const int* row_sta
                              const unsigned char* vertex_class, long long M, long long N, int row_floats, float factor,
                              float max_displacement, float* Y, void* stream);
 
+/* Vertex normals and per-vertex colour from the full-resolution images (csrc/mesh_colour.hip; semantics in
+ * mvsnet_amd/mesh_colour.py).  M vertices, 0..2^31-1, and F faces with 3 F <= 2^31-1 (negative: MVS_E_BADARG, beyond:
+ * MVS_E_SHAPE); E = 3 F.  A pointer to an array of M, F, E or V entries may be NULL when that size is 0.  The caller sorts
+ * between the first two calls and rasterises the depth maps (mvs_raster_mesh_f32, cull 0) before the third:
+ *   mvs_mesh_normals_keys_i64   vertices (M,3) float32, faces (F,3) int32 -> keys (E) int64: per valid face (indices in 0..M-1
+ *                 and pairwise different, nine finite coordinates) int64(vertex) << 31 | f for its three corners, INT64_MAX
+ *                 three times otherwise.  Clears the status words; counts word 0
+ *   (an ascending sort of keys -> sorted_keys (E) int64)
+ *   mvs_mesh_normals_f32        -> normals (M,3) float32: per vertex the float64 sum of (b - a) x (c - a) over its run of
+ *                 faces, ascending, normalised and rounded once; (0,0,0) where the run is empty or the length is 0 or not
+ *                 finite.  Counts word 1
+ *   mvs_mesh_colour_accumulate_f32  V views of H x W (H, W <= 2^20, V H W <= 2^31-1: else MVS_E_SHAPE), in ascending order: proj
+ *                 (V,12) float32 as render.projection_tables gives it, centres (V,3) float32, depth (V,H,W) float32, images
+ *                 (V,H,W,3) uint8 (byte offsets in 64 bits); min_depth >= 0 and ratio > 0 finite, min_cos in [-1, 1], power
+ *                 0..8 (else MVS_E_BADARG).  Every vertex a view sees adds its weighted bilinear sample to acc (M,4) float64
+ *                 (16-byte aligned: three channel sums and the weight) and 1 to seen (M) int32; both continue what they hold,
+ *                 so the caller zeroes them before the first call of a mesh.  acc and seen must not be one of the inputs
+ *   mvs_mesh_colour_finish_u8   colours (M,3) uint8 or NULL, acc, seen -> out (M,3) uint8 (never one of the inputs): the byte
+ *                 floor(acc[k] / acc[3] + 1/2) clamped to 0..255 where seen > 0 and acc[3] > 0, else the input colour, or 0
+ *                 without one.  Counts word 2
+ *   workspace     mvs_mesh_colour_workspace_bytes(M, F) bytes (0 for invalid sizes): 64 int32 status words (0 invalid faces,
+ *                 1 vertices with a zero normal, 2 vertices no view saw); each call clears the words it counts.  The
+ *                 accumulation counts nothing and takes no workspace
+ * All four only enqueue on `stream`: nothing is allocated, nothing synchronised.  The only atomics are integer counts; a
+ * vertex's sums run in one lane in the order of the views, so the same inputs give the same bytes on any grid, and two calls
+ * over two halves of the views give the bytes of one call over all.  Every argument is checked before the first GPU call and
+ * the outputs are untouched on error.  Every index read from an array (faces, the face of a key) is range-checked before it
+ * is used, and a pixel is compared with the image in float32 before it is converted. */
+size_t mvs_mesh_colour_workspace_bytes(long long M, long long F);
+int mvs_mesh_normals_keys_i64(const float* vertices, long long M, const int* faces, long long F, long long* keys, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int mvs_mesh_normals_f32(const float* vertices, long long M, const int* faces, long long F, const long long* sorted_keys,
+                         float* normals, void* workspace, size_t workspace_bytes, void* stream);
+int mvs_mesh_colour_accumulate_f32(const float* vertices, const float* normals, long long M, const float* proj,
+                                   const float* centres, int V, int H, int W, const float* depth, const unsigned char* images,
+                                   float min_depth, float ratio, float min_cos, int power, double* acc, int* seen, void* stream);
+int mvs_mesh_colour_finish_u8(const unsigned char* colours, const double* acc, const int* seen, long long M, unsigned char* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,13 @@ SIGNATURES = {
     "mvs_mesh_smooth_heads_i64": (_i, [_p, _ll, _p, _p, _sz, _p]),
     "mvs_mesh_smooth_rows_i32": (_i, [_p, _p, _p, _ll, _ll, _i, _p, _p, _p, _p, _sz, _p]),
     "mvs_mesh_smooth_step_f32": (_i, [_p, _p, _p, _p, _p, _ll, _ll, _i, _f, _f, _p, _p]),
+    # vertex normals and colour from the images (csrc/mesh_colour.hip; the header has it last), before mvs_fusion_workspace_bytes
+    # for the same reason; its arena cases and pin are tests/test_gpu_arena_mesh_colour.py
+    "mvs_mesh_colour_workspace_bytes": (_sz, [_ll, _ll]),
+    "mvs_mesh_normals_keys_i64": (_i, [_p, _ll, _p, _ll, _p, _p, _sz, _p]),
+    "mvs_mesh_normals_f32": (_i, [_p, _ll, _p, _ll, _p, _p, _p, _sz, _p]),
+    "mvs_mesh_colour_accumulate_f32": (_i, [_p, _p, _ll, _p, _p, _i, _i, _i, _p, _p, _f, _f, _f, _i, _p, _p, _p]),
+    "mvs_mesh_colour_finish_u8": (_i, [_p, _p, _p, _ll, _p, _p, _sz, _p]),
     "mvs_fusion_workspace_bytes": (_sz, [_i] * 5),
     "mvs_fusion_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "mvs_depth_normals_f32": (_i, [_p, _p, _i, _i, _i, _p, _f, _f, _p, _p]),

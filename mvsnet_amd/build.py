@@ -18,7 +18,7 @@ SOURCES = ["homography.hip", "cost_volume.hip", "conv3d_scalar.hip", "conv3d_mfm
            "regnet.hip", "library.hip", "softargmin.hip", "gru.hip", "gru_mfma.hip", "gru_fused.hip", "gru_streams.hip", "gru_sweep.hip", "unet2d.hip", "unet2d_p.hip", "center_images.hip", "multi_tensor.hip",
            "backward.hip", "groupnorm.hip", "optimizer.hip", "conv3d_wgrad.hip", "conv3d_c1.hip", "conv3d_k8.hip", "gru_train.hip", "conv2d_wgrad.hip",
            "fusion.hip", "pointcloud.hip", "render.hip", "view_selection.hip", "tsdf.hip", "raster.hip", "mesh_components.hip", "mesh_simplify.hip", "mesh_sample.hip",
-           "mesh_smooth.hip"]
+           "mesh_smooth.hip", "mesh_colour.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 FLAGS += os.environ.get("MVS_EXTRA_HIPCC_FLAGS", "").split()      # developer builds (tools/README.md)

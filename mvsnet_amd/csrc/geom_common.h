@@ -87,6 +87,20 @@ __device__ __forceinline__ int geo_block_sum(int v, int* sh) {
     return total;
 }
 
+// ------------------------------------------------------------------------------------------------ sorted keys
+// The first position in the ascending keys[0..n) whose key is >= want: a binary search of at most 32 steps inside 0..n-1, no
+// atomics.  Keys of the form int64(owner) << 31 | item sort the items of one owner into a run, bounded by the lower bounds
+// of owner << 31 and (owner + 1) << 31.
+__device__ __forceinline__ long long geo_lower_bound(const long long* __restrict__ keys, long long n, long long want) {
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (keys[mid] < want) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 namespace {
 
 // One lane per pixel of all views: keys -> depth (0 where empty) and index (-1 where empty).  index may be NULL.

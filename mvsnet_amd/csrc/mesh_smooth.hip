@@ -124,13 +124,7 @@ __global__ __launch_bounds__(SM_THREADS) void sm_starts_kernel(const long long* 
                                                                 int* __restrict__ row_start) {
     const long long v = (long long)blockIdx.x * SM_THREADS + threadIdx.x;
     if (v > M) return;
-    const long long want = v << 31;
-    long long lo = 0, hi = E;                                                  // the first position whose key is >= want
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (sorted_keys[mid] < want) lo = mid + 1;
-        else hi = mid;
-    }
+    const long long lo = geo_lower_bound(sorted_keys, E, v << 31);             // the first position whose key is >= v << 31
     row_start[v] = lo > 0 ? head_rank[lo - 1] : 0;
 }
 

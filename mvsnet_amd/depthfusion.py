@@ -18,6 +18,7 @@ points_mvsnet/consistencyCheck-<YYYYmmdd-HHMMSS>/final3d_model.ply, the path the
         [--mesh_min_component_faces 0] [--mesh_min_component_extent 0] [--mesh_keep_largest 0] [--mesh_simplify_voxels S]
         [--mesh_smooth_iterations N [--mesh_smooth_lambda 0.5] [--mesh_smooth_mu -0.53] [--mesh_smooth_boundary fixed|curve|free]
          [--mesh_smooth_max_voxels 1]]
+        [--mesh_recolour [--mesh_recolour_min_cos 0.2] [--mesh_recolour_angle_power 2] [--mesh_recolour_occlusion_rel 0.01]]
         [--eval_gt G.ply [--eval_max_dist 20] [--eval_thresholds 0.5,1,2] [--mesh_eval_spacing s]]
         [--normals] [--normal_angle_threshold DEG] [--jump_threshold 0.05] [--write_normal_maps]
 --normals estimates surface normals from the depth maps on the GPU and writes the PLY as x y z nx ny nz red green blue
@@ -142,7 +143,7 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
 def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, depth_rel_threshold, num_consistent,
                dedupe=True, fusion_sources="all", eval_gt=None, eval_max_dist=20.0, eval_thresholds=(), normals=False,
                normal_angle_threshold=None, jump_threshold=0.05, write_normal_maps=False, mesh=False, mesh_clean=None,
-               mesh_simplify_voxels=None, mesh_eval_spacing=None, mesh_smooth=None):
+               mesh_simplify_voxels=None, mesh_eval_spacing=None, mesh_smooth=None, mesh_recolour=None):
     """--fusion hip: mvsnet_amd.fusion over depths_mvsnet/ -> <point_folder>/consistencyCheck-<time>/final3d_model.ply
     (with normals: x y z nx ny nz red green blue; write_normal_maps: depths_mvsnet/<idx>_normal.pfm, camera frame).
     With eval_gt (a PLY), the fused cloud is evaluated against it on the device (mvsnet_amd.evaluate) and the metrics are
@@ -150,7 +151,8 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
     nets of the same depth maps under the same consistency criteria; mesh_clean = dict(min_component_faces=,
     min_component_extent=, keep_largest=) removes its small pieces (mvsnet_amd.mesh_clean) and mesh_simplify_voxels = S clusters
     its vertices in cells of S voxels (mvsnet_amd.mesh_simplify); mesh_smooth = dict(iterations=, lam=, mu=, boundary=,
-    max_voxels=) smooths it in between (mvsnet_amd.mesh_smooth).  With mesh, eval_gt and mesh_eval_spacing = s the mesh, as it
+    max_voxels=) smooths it in between (mvsnet_amd.mesh_smooth) and mesh_recolour = dict(min_cos=, angle_power=, occlusion_rel=)
+    takes its colours from the full-resolution images as the last stage (mvsnet_amd.mesh_colour).  With mesh, eval_gt and mesh_eval_spacing = s the mesh, as it
     is written, is evaluated against the same ground truth by its surface samples at spacing s (mvsnet_amd.mesh_sample) into
     mesh_metrics.json beside mesh.ply; metrics.json stays the cloud's."""
     import json
@@ -187,7 +189,8 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
         print("meshed: %s" % json.dumps(mesh_dense_folder(
             dense_folder, os.path.join(out, "mesh.ply"), fusion_sources=fusion_sources, prob_threshold=prob_threshold,
             reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent,
-            simplify_voxels=mesh_simplify_voxels, **smooth_options(mesh_smooth), **dict(
+            simplify_voxels=mesh_simplify_voxels, **smooth_options(mesh_smooth),
+            **({} if mesh_recolour is None else dict(recolour=mesh_recolour)), **dict(
                 mesh_clean or {}, **({} if mesh_eval_spacing is None else dict(
                     eval_gt=eval_gt, eval_spacing=mesh_eval_spacing, eval_max_dist=eval_max_dist, eval_thresholds=eval_thresholds))))))
     return path
@@ -233,7 +236,16 @@ def main(argv=None):
     add_sampling(ap, "mesh_eval_")
     from .mesh_smooth import add_options as add_smoothing, check_smooth_arguments
     add_smoothing(ap, "mesh_")
+    from .mesh_colour import add_options as add_recolouring, check_recolour_arguments
+    add_recolouring(ap, "mesh_")
     a = ap.parse_args(argv)
+    for name in ("", "_min_cos", "_angle_power", "_occlusion_rel"):
+        if getattr(a, "mesh_recolour" + name) != ap.get_default("mesh_recolour" + name) and not a.mesh:
+            raise SystemExit("--mesh_recolour%s needs --mesh" % name)
+    try:
+        mesh_recolour = check_recolour_arguments(a, "mesh_")
+    except ValueError as e:
+        raise SystemExit(str(e))
     for name in ("iterations", "lambda", "mu", "boundary", "max_voxels"):
         if getattr(a, "mesh_smooth_" + name) != ap.get_default("mesh_smooth_" + name) and not a.mesh:
             raise SystemExit("--mesh_smooth_%s needs --mesh" % name)
@@ -301,7 +313,8 @@ def main(argv=None):
                           jump_threshold=0.05 if a.jump_threshold is None else a.jump_threshold,
                           write_normal_maps=a.write_normal_maps, mesh=a.mesh,
                           mesh_clean=dict(min_component_faces=clean[0], min_component_extent=clean[1], keep_largest=clean[2]),
-                          mesh_simplify_voxels=a.mesh_simplify_voxels, mesh_eval_spacing=a.mesh_eval_spacing, mesh_smooth=mesh_smooth)
+                          mesh_simplify_voxels=a.mesh_simplify_voxels, mesh_eval_spacing=a.mesh_eval_spacing, mesh_smooth=mesh_smooth,
+                          mesh_recolour=mesh_recolour)
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")

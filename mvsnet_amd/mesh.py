@@ -65,6 +65,11 @@ float32(S voxel), aligned to the volume's origin.  Without it nothing of it runs
 A score: with eval_gt (a ground-truth cloud, PLY) and eval_spacing = s the mesh, as it is written (after the removal of small
 pieces, the smoothing and the simplification), is evaluated by its surface samples at spacing s (mvsnet_amd.mesh_sample, then
 mvsnet_amd.evaluate) and the metrics go to mesh_metrics.json beside the PLY.  Without them nothing of it runs.
+
+Colour from the images: with recolour the mesh, as the last stage (after the removal of small pieces, the smoothing and the
+simplification), takes its vertex colours from the full-resolution images through mvsnet_amd.mesh_colour (its docstring has the
+semantics): a weighted mean over the views that see each vertex, occlusion resolved by the rasteriser.  Without it nothing of it
+runs and the mesh bytes are unchanged.
 """
 from __future__ import annotations
 
@@ -281,14 +286,16 @@ class TsdfVolume:
             _lib.check(rc, "mvs_tsdf_integrate_f32")
         return self
 
-    def extract(self, min_count=1, clean=None, simplify=None, smooth=None):
+    def extract(self, min_count=1, clean=None, simplify=None, smooth=None, recolour=None):
         """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation.  With
         clean = dict(min_faces=, min_extent=, keep_largest=) the mesh goes through mesh_clean.clean_mesh on the device before
         the copy to the host and the result is (vertices, colours, faces, report).  With simplify = cell (world units) it then
         goes through mesh_simplify.simplify_device with cells aligned to the volume's origin; the result is (vertices, colours,
         faces, report) with the simplification's report under "simplify", beside the cleaning's fields if there are any.  With
         smooth = dict(iterations=, lam=, mu=, boundary=, max_displacement=) (mesh_smooth.check_options) the mesh goes through
-        mesh_smooth.smooth_device after the cleaning and before the simplification; its report goes under "smooth"."""
+        mesh_smooth.smooth_device after the cleaning and before the simplification; its report goes under "smooth".  With
+        recolour = dict(cams=, images=, and mesh_colour.check_options' options) the mesh, as the last stage, takes its colours
+        from the images through mesh_colour.colour_device (cams at the images' scale); its report goes under "recolour"."""
         import torch
         from . import _lib
         min_count = check_min_count(min_count)
@@ -301,6 +308,11 @@ class TsdfVolume:
         if smooth is not None:
             from . import mesh_smooth
             smooth = mesh_smooth.check_options(**smooth)
+        if recolour is not None:
+            from . import mesh_colour
+            recolour = dict(recolour)
+            views = mesh_colour._view_list(recolour.pop("cams"), recolour.pop("images"))
+            recolour = mesh_colour.check_options(**recolour)
         lib = _lib.load()
         nx, ny, nz = self.dims
         nodes = nx * ny * nz
@@ -338,6 +350,10 @@ class TsdfVolume:
                 vertices, colours, faces, simplified = mesh_simplify.simplify_device(vertices, colours, faces, self.dev, simplify,
                                                                                      self.origin)
                 report = dict(report or {}, simplify=simplified)
+            if recolour is not None:
+                vertices, colours, faces, recoloured = mesh_colour.colour_device(vertices, colours, faces, self.dev, views[0], views[1],
+                                                                                 *recolour)
+                report = dict(report or {}, recolour=recoloured)
             mesh = (vertices.cpu().numpy(), colours.cpu().numpy(), faces.cpu().numpy())
             return mesh if report is None else mesh + (report,)
 
@@ -379,7 +395,9 @@ def mesh_depth_maps(depths, probs, cams, images=None, **options):
     voxel, resolution, bounds, trunc_voxels, num_consistent, prob_threshold, reproj_threshold, depth_rel_threshold, sources,
     min_count, device, min_component_faces, min_component_extent, keep_largest (all 0: no cleaning runs), and simplify_voxels
     (None or 0: no simplification runs; S > 0: vertex clustering in cells of float32(S voxel)), and smooth_iterations (0: no
-    smoothing runs) with smooth_lambda, smooth_mu, smooth_boundary and smooth_max_voxels (the bound is float32(R voxel))."""
+    smoothing runs) with smooth_lambda, smooth_mu, smooth_boundary and smooth_max_voxels (the bound is float32(R voxel)), and
+    recolour (None or False: nothing of it runs; True or a dict of mesh_colour.check_options' options: the colours come from
+    `images` at their own size, as the last stage, the cameras brought to the images' scale)."""
     return _mesh_depth_maps(depths, probs, cams, images, **options)[:3]
 
 
@@ -387,7 +405,7 @@ def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution
                      num_consistent=3, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, sources=None,
                      min_count=1, device=None, min_component_faces=0, min_component_extent=0.0, keep_largest=0,
                      simplify_voxels=None, smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed",
-                     smooth_max_voxels=1.0):
+                     smooth_max_voxels=1.0, recolour=None):
     """mesh_depth_maps -> (vertices, colours, faces, the report of the cleaning, the smoothing and the simplification or None)."""
     from . import mesh_clean, mesh_simplify, mesh_smooth
     simplify_voxels = mesh_simplify.check_voxels(simplify_voxels)
@@ -396,6 +414,14 @@ def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution
     if smooth_iterations:
         smooth_max_voxels = mesh_smooth.check_voxels(smooth_max_voxels)
         mesh_smooth.check_options(smooth_iterations, smooth_lambda, smooth_mu, smooth_boundary)      # before any GPU work
+    if recolour is None or recolour is False:
+        recolour = None
+    else:
+        from . import mesh_colour
+        recolour = {} if recolour is True else dict(recolour)
+        mesh_colour.check_options(**recolour)                                  # before any GPU work
+        if images is None:
+            raise ValueError("recolour needs the images")
     from .fusion import FusionPlan
     clean = mesh_clean.check_options(min_component_faces, min_component_extent, keep_largest)
     clean = dict(zip(mesh_clean.OPTION_NAMES, clean)) if mesh_clean.wanted(*clean) else None
@@ -426,13 +452,17 @@ def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution
         origin, voxel, dims = choose_volume(bounds[0], bounds[1], voxel, resolution)
     vol = TsdfVolume(origin, voxel, dims, tv * voxel, colour=images is not None, device=device)
     vol.integrate(depths, probs, cams, images, prob_threshold=prob_threshold)
-    if clean is None and simplify_voxels is None and not smooth_iterations:
+    if clean is None and simplify_voxels is None and not smooth_iterations and recolour is None:
         return vol.extract(min_count) + (None,)
+    if recolour is not None:
+        at = [tuple(int(n) for n in im.shape[:2]) for im in images]
+        scaled = np.stack([mesh_colour.scale_cams(np.asarray(cams, np.float64)[k:k + 1], depths.shape[1:3], at[k])[0] for k in range(len(at))])
+        recolour = dict(recolour, cams=scaled, images=images)
     cell = None if simplify_voxels is None else float(np.float32(simplify_voxels * vol.voxel))
     if smooth_iterations:
         smooth = dict(iterations=smooth_iterations, lam=smooth_lambda, mu=smooth_mu, boundary=smooth_boundary,
                       max_displacement=float(np.float32(smooth_max_voxels * vol.voxel)))
-    return vol.extract(min_count, clean=clean, simplify=cell, smooth=smooth)
+    return vol.extract(min_count, clean=clean, simplify=cell, smooth=smooth, recolour=recolour)
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -458,6 +488,8 @@ def build_parser():
     add_option(ap)
     from .mesh_smooth import add_options as add_smoothing
     add_smoothing(ap)
+    from .mesh_colour import add_options as add_recolouring
+    add_recolouring(ap)
     ap.add_argument("--eval_gt", default=None, help="ground-truth cloud (PLY): evaluate the mesh's surface samples against it "
                     "(mesh_metrics.json beside the output; needs --eval_spacing)")
     from .mesh_sample import add_options as add_sampling
@@ -492,6 +524,8 @@ def parse_args(argv=None):
             raise ValueError("--simplify_voxels must be positive and finite, got %r" % (a.simplify_voxels,))
         from .mesh_smooth import check_smooth_arguments
         a.smooth = check_smooth_arguments(a)                                   # None: --smooth_iterations 0, nothing of it runs
+        from .mesh_colour import check_recolour_arguments
+        a.recolour_options = check_recolour_arguments(a)                       # None: no --recolour, nothing of it runs
         if (a.eval_gt is None) != (a.eval_spacing is None):
             raise ValueError("--eval_gt and --eval_spacing go together")
         try:
@@ -579,6 +613,7 @@ def main(argv=None):
                                    prob_threshold=a.prob_threshold, min_count=a.min_count,
                                    min_component_faces=a.min_component_faces, min_component_extent=a.min_component_extent,
                                    keep_largest=a.keep_largest, simplify_voxels=a.simplify_voxels, **smooth_options(a.smooth),
+                                   **({} if a.recolour_options is None else dict(recolour=a.recolour_options)),
                                    **({} if a.eval_gt is None else dict(eval_gt=a.eval_gt, eval_spacing=a.eval_spacing,
                                                                         eval_max_dist=a.eval_max_dist, eval_thresholds=a.eval_thresholds)))
     except (ValueError, OSError) as e:
