@@ -148,13 +148,12 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
     (with normals: x y z nx ny nz red green blue; write_normal_maps: depths_mvsnet/<idx>_normal.pfm, camera frame).
     With eval_gt (a PLY), the fused cloud is evaluated against it on the device (mvsnet_amd.evaluate) and the metrics are
     written to metrics.json next to the PLY.  With mesh, mvsnet_amd.mesh writes mesh.ply beside it: TSDF fusion and surface
-    nets of the same depth maps under the same consistency criteria; mesh_clean = dict(min_component_faces=,
-    min_component_extent=, keep_largest=) removes its small pieces (mvsnet_amd.mesh_clean) and mesh_simplify_voxels = S clusters
-    its vertices in cells of S voxels (mvsnet_amd.mesh_simplify); mesh_smooth = dict(iterations=, lam=, mu=, boundary=,
-    max_voxels=) smooths it in between (mvsnet_amd.mesh_smooth) and mesh_recolour = dict(min_cos=, angle_power=, occlusion_rel=)
-    takes its colours from the full-resolution images as the last stage (mvsnet_amd.mesh_colour).  With mesh, eval_gt and mesh_eval_spacing = s the mesh, as it
-    is written, is evaluated against the same ground truth by its surface samples at spacing s (mvsnet_amd.mesh_sample) into
-    mesh_metrics.json beside mesh.ply; metrics.json stays the cloud's."""
+    nets of the same depth maps under the same consistency criteria, then the stages of mvsnet_amd.mesh.STAGES that are asked
+    for, in that table's order: mesh_clean = dict(min_component_faces=, min_component_extent=, keep_largest=),
+    mesh_simplify_voxels = S, mesh_smooth = dict(iterations=, lam=, mu=, boundary=, max_voxels=) and mesh_recolour =
+    dict(min_cos=, angle_power=, occlusion_rel=), the last two as their modules' check_arguments give them.  With mesh, eval_gt and mesh_eval_spacing = s the mesh, as it is written, is evaluated against the same
+    ground truth by its surface samples at spacing s (mvsnet_amd.mesh_sample) into mesh_metrics.json beside mesh.ply;
+    metrics.json stays the cloud's."""
     import json
     import time
     from . import fusion
@@ -185,23 +184,20 @@ def hip_fusion(dense_folder, point_folder, prob_threshold, reproj_threshold, dep
             f.write(json.dumps(metrics) + "\n")
         print("evaluated against %s: %s" % (eval_gt, json.dumps(metrics)))
     if mesh:
-        from .mesh import mesh_dense_folder, smooth_options
+        from .mesh import mesh_dense_folder, stage_keywords
+        options = dict(mesh_clean or {}, simplify_voxels=mesh_simplify_voxels)
+        options.update(stage_keywords(dict(smooth=mesh_smooth, recolour=mesh_recolour)))
+        if mesh_eval_spacing is not None:
+            options.update(eval_gt=eval_gt, eval_spacing=mesh_eval_spacing, eval_max_dist=eval_max_dist, eval_thresholds=eval_thresholds)
         print("meshed: %s" % json.dumps(mesh_dense_folder(
             dense_folder, os.path.join(out, "mesh.ply"), fusion_sources=fusion_sources, prob_threshold=prob_threshold,
-            reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent,
-            simplify_voxels=mesh_simplify_voxels, **smooth_options(mesh_smooth),
-            **({} if mesh_recolour is None else dict(recolour=mesh_recolour)), **dict(
-                mesh_clean or {}, **({} if mesh_eval_spacing is None else dict(
-                    eval_gt=eval_gt, eval_spacing=mesh_eval_spacing, eval_max_dist=eval_max_dist, eval_thresholds=eval_thresholds))))))
+            reproj_threshold=reproj_threshold, depth_rel_threshold=depth_rel_threshold, num_consistent=num_consistent, **options)))
     return path
 
 
-def _gpu_ready():                              # the old private name of _lib.gpu_ready, kept for its callers
-    from ._lib import gpu_ready
-    return gpu_ready()
-
-
-def main(argv=None):
+def _build_parser():
+    """-> (the parser, [(stage, its actions)] for the --mesh_* flags of mvsnet_amd.mesh's stages added before --mesh_eval_spacing,
+    the same for those after it): the stages by age, as in mvsnet_amd.mesh's own parser; a new one goes last."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dense_folder", type=str, required=True)
     ap.add_argument("--fusibile_exe_path", type=str, default="")
@@ -228,53 +224,51 @@ def main(argv=None):
                     help="--fusion hip: write depths_mvsnet/<idx>_normal.pfm (colour PFM, camera frame)")
     ap.add_argument("--mesh", action="store_true",
                     help="--fusion hip: also write mesh.ply beside final3d_model.ply (mvsnet_amd.mesh, default options)")
-    from .mesh_clean import add_options, check_options
-    add_options(ap, "mesh_")
-    from .mesh_simplify import add_option, check_voxels
-    add_option(ap, "mesh_")
-    from .mesh_sample import add_options as add_sampling, check_spacing
-    add_sampling(ap, "mesh_eval_")
-    from .mesh_smooth import add_options as add_smoothing, check_smooth_arguments
-    add_smoothing(ap, "mesh_")
-    from .mesh_colour import add_options as add_recolouring, check_recolour_arguments
-    add_recolouring(ap, "mesh_")
+    from .mesh import FLAG_ORDER
+    from .mesh_sample import add_options as add_sampling
+    early = [(stage, stage.module.add_options(ap, "mesh_")) for stage in FLAG_ORDER[:2]]
+    add_sampling(ap, "mesh_eval_")                                             # stands here since before the later stages came
+    late = [(stage, stage.module.add_options(ap, "mesh_")) for stage in FLAG_ORDER[2:]]
+    return ap, early, late
+
+
+def build_parser():
+    return _build_parser()[0]
+
+
+def main(argv=None):
+    from .mesh import stage_keywords
+    ap, early, late = _build_parser()
     a = ap.parse_args(argv)
-    for name in ("", "_min_cos", "_angle_power", "_occlusion_rel"):
-        if getattr(a, "mesh_recolour" + name) != ap.get_default("mesh_recolour" + name) and not a.mesh:
-            raise SystemExit("--mesh_recolour%s needs --mesh" % name)
-    try:
-        mesh_recolour = check_recolour_arguments(a, "mesh_")
-    except ValueError as e:
-        raise SystemExit(str(e))
-    for name in ("iterations", "lambda", "mu", "boundary", "max_voxels"):
-        if getattr(a, "mesh_smooth_" + name) != ap.get_default("mesh_smooth_" + name) and not a.mesh:
-            raise SystemExit("--mesh_smooth_%s needs --mesh" % name)
-    try:
-        mesh_smooth = check_smooth_arguments(a, "mesh_")
-    except ValueError as e:
-        raise SystemExit(str(e))
+    mesh_stages = {}
+
+    def need_mesh(actions):                                                    # a stage's flag away from its default asks for a mesh
+        for action in actions:
+            if getattr(a, action.dest) != action.default and not a.mesh:
+                raise SystemExit("%s needs --mesh" % action.option_strings[0])
+
+    def check(stage):
+        try:
+            mesh_stages[stage.name] = stage.module.check_arguments(a, "mesh_")
+        except ValueError as e:
+            raise SystemExit(str(e))
+
+    # The checks go from the newest flag to the oldest, and say the same as ever when several things are wrong at once: the
+    # stages after --mesh_eval_spacing ask for --mesh before they check their values, the older ones after.
+    for stage, actions in reversed(late):
+        need_mesh(actions)
+        check(stage)
     if a.mesh_eval_spacing is not None:
         if not (a.mesh and a.eval_gt):
             raise SystemExit("--mesh_eval_spacing needs --mesh and --eval_gt")
+        from .mesh_sample import check_spacing
         try:
             check_spacing(a.mesh_eval_spacing)
         except ValueError as e:
             raise SystemExit("--mesh_eval_spacing: %s" % e)
-    try:
-        if a.mesh_simplify_voxels is not None and check_voxels(a.mesh_simplify_voxels) is None:
-            raise ValueError("0 given")
-    except ValueError as e:
-        raise SystemExit("--mesh_simplify_voxels must be positive and finite (%s)" % e)
-    if a.mesh_simplify_voxels is not None and not a.mesh:
-        raise SystemExit("--mesh_simplify_voxels needs --mesh")
-    try:
-        clean = check_options(a.mesh_min_component_faces, a.mesh_min_component_extent, a.mesh_keep_largest)
-    except ValueError as e:
-        raise SystemExit("--mesh_min_component_faces and --mesh_keep_largest must be integers >= 0, --mesh_min_component_extent "
-                         "finite and >= 0 (%s)" % e)
-    for flag, given in zip(("--mesh_min_component_faces", "--mesh_min_component_extent", "--mesh_keep_largest"), clean):
-        if given and not a.mesh:
-            raise SystemExit("%s needs --mesh" % flag)
+    for stage, actions in reversed(early):
+        check(stage)
+        need_mesh(actions)
     if a.fusion != "hip":
         for flag, given in (("--mesh", a.mesh), ("--normals", a.normals), ("--normal_angle_threshold", a.normal_angle_threshold is not None),
                             ("--jump_threshold", a.jump_threshold is not None), ("--write_normal_maps", a.write_normal_maps)):
@@ -297,7 +291,8 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit("--eval_gt: %s" % e)
     if a.fusion == "hip":
-        why = _gpu_ready()
+        from ._lib import gpu_ready
+        why = gpu_ready()
         if why is not None:
             raise SystemExit("--fusion hip needs a GPU and the HIP library: %s" % why)
     point_folder = os.path.join(a.dense_folder, "points_mvsnet")
@@ -311,10 +306,9 @@ def main(argv=None):
                           eval_max_dist=a.eval_max_dist, eval_thresholds=eval_thresholds, normals=a.normals,
                           normal_angle_threshold=a.normal_angle_threshold,
                           jump_threshold=0.05 if a.jump_threshold is None else a.jump_threshold,
-                          write_normal_maps=a.write_normal_maps, mesh=a.mesh,
-                          mesh_clean=dict(min_component_faces=clean[0], min_component_extent=clean[1], keep_largest=clean[2]),
-                          mesh_simplify_voxels=a.mesh_simplify_voxels, mesh_eval_spacing=a.mesh_eval_spacing, mesh_smooth=mesh_smooth,
-                          mesh_recolour=mesh_recolour)
+                          write_normal_maps=a.write_normal_maps, mesh=a.mesh, mesh_eval_spacing=a.mesh_eval_spacing,
+                          mesh_clean=stage_keywords(dict(clean=mesh_stages["clean"])), mesh_simplify_voxels=a.mesh_simplify_voxels,
+                          mesh_smooth=mesh_stages["smooth"], mesh_recolour=mesh_stages["recolour"])
     print("Convert mvsnet output to gipuma input")
     mvsnet_to_gipuma(a.dense_folder, point_folder)
     print("Run depth map fusion & filter")

@@ -343,12 +343,13 @@ def _surface(points, faces, spacing, name, device):
         raise ValueError("%s_faces and %s_spacing go together" % (name, name))
     import torch
     from . import _lib, mesh_sample
-    from .mesh_clean import _inputs
+    from .mesh_common import inputs
     density = mesh_sample.check_spacing(spacing)
     if not hasattr(points, "shape") or not hasattr(faces, "shape"):
         raise ValueError("%s and %s_faces must be arrays or tensors" % (name, name))
+    what = "point-cloud evaluation"
     mesh_sample._shapes(points, None, faces)
-    dev, v, _, f = _inputs(points, None, faces, _lib.device(device, "point-cloud evaluation"))
+    dev, v, _, f = inputs(points, None, faces, _lib.device(device, what), what, mesh_sample._shapes)   # None: the current device
     with torch.cuda.device(dev):
         out, stats = mesh_sample.sample_device(v, None, f, dev, density)
     return out["xyz"], dict(stats, spacing=float(spacing))

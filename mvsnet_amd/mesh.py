@@ -74,6 +74,7 @@ runs and the mesh bytes are unchanged.
 from __future__ import annotations
 
 import argparse
+import collections
 import ctypes
 import json
 import math
@@ -81,6 +82,9 @@ import os
 import sys
 
 import numpy as np
+
+from . import mesh_clean, mesh_colour, mesh_simplify, mesh_smooth
+from .mesh_common import need_gpu, refuse_existing
 
 MAX_NODES = 2 ** 31 - 1
 
@@ -220,6 +224,98 @@ def _check_views(depths, probs, cams, images):
     return ds
 
 
+# ------------------------------------------------------------------------------------------------ the stages after the extraction
+
+# One row per stage, in the order in which the stages run.  Everything else that knows the chain is a loop over this table:
+# TsdfVolume.extract, _mesh_depth_maps, the parser and parse_args below, and depthfusion.py's --mesh_* flags.  A stage's module
+# has add_options(ap, prefix) -> its actions, check_arguments(namespace, prefix) -> its options in the units the flags carry
+# (voxels) or None when it is off, check_options and a device function (vertices, colours, faces, dev, *arguments) ->
+# (vertices, colours, faces, report); the row adds what only this file knows, the volume:
+#   key        where the stage's report goes in the merged report (None: its fields at top level)
+#   since      the stages by age, which is the order of their flags in --help and of their checks (FLAG_ORDER)
+#   keywords   check_arguments' options -> the keywords of mesh_depth_maps and mesh_dense_folder that ask for the same
+#   options    those keywords (popped from a dict, absent ones at their defaults), and the images -> the options, checked, or None
+#   world      (volume, options, (cams, images, depth size)) -> what extract takes under the stage's name, in world units
+#   arguments  (volume, that value) -> the checked arguments of the device function
+Stage = collections.namedtuple("Stage", "name module device key since keywords options world arguments")
+
+
+def _clean_options(kw, images):
+    o = mesh_clean.check_options(kw.pop("min_component_faces", 0), kw.pop("min_component_extent", 0.0), kw.pop("keep_largest", 0))
+    return dict(zip(mesh_clean.OPTION_NAMES, o)) if mesh_clean.wanted(*o) else None
+
+
+def _smooth_options(kw, images):
+    iterations = mesh_smooth.check_iterations(kw.pop("smooth_iterations", 0), least=0)
+    lam, mu, boundary, max_voxels = (kw.pop("smooth_" + name, default) for name, default in
+                                     (("lambda", 0.5), ("mu", -0.53), ("boundary", "fixed"), ("max_voxels", 1.0)))
+    if not iterations:
+        return None
+    max_voxels = mesh_smooth.check_voxels(max_voxels)
+    mesh_smooth.check_options(iterations, lam, mu, boundary)
+    return dict(iterations=iterations, lam=lam, mu=mu, boundary=boundary, max_voxels=max_voxels)
+
+
+def _simplify_options(kw, images):
+    voxels = mesh_simplify.check_voxels(kw.pop("simplify_voxels", None))
+    return None if voxels is None else dict(voxels=voxels)
+
+
+def _recolour_options(kw, images):
+    o = kw.pop("recolour", None)
+    if o is None or o is False:
+        return None
+    o = {} if o is True else dict(o)
+    mesh_colour.check_options(**o)
+    if images is None:
+        raise ValueError("recolour needs the images")
+    return o
+
+
+def _recolour_world(vol, o, views):
+    """The cameras brought to each image's own size."""
+    cams, images, size = views
+    at = [tuple(int(n) for n in im.shape[:2]) for im in images]
+    scaled = np.stack([mesh_colour.scale_cams(np.asarray(cams, np.float64)[k:k + 1], size, at[k])[0] for k in range(len(at))])
+    return dict(o, cams=scaled, images=images)
+
+
+def _recolour_arguments(vol, o):
+    o = dict(o)
+    cams, images, _ = mesh_colour._view_list(o.pop("cams"), o.pop("images"))
+    return (cams, images) + mesh_colour.check_options(**o)
+
+
+STAGES = (
+    Stage("clean", mesh_clean, mesh_clean.clean_device, None, 1,
+          lambda o: dict(min_component_faces=o["min_faces"], min_component_extent=o["min_extent"], keep_largest=o["keep_largest"]),
+          _clean_options, lambda vol, o, views: o, lambda vol, o: mesh_clean.check_options(**o)),
+    Stage("smooth", mesh_smooth, mesh_smooth.smooth_device, "smooth", 3,
+          lambda o: dict(smooth_iterations=o["iterations"], smooth_lambda=o["lam"], smooth_mu=o["mu"], smooth_boundary=o["boundary"],
+                         smooth_max_voxels=o["max_voxels"]),
+          _smooth_options,
+          lambda vol, o, views: dict(iterations=o["iterations"], lam=o["lam"], mu=o["mu"], boundary=o["boundary"],
+                                     max_displacement=float(np.float32(o["max_voxels"] * vol.voxel))),
+          lambda vol, o: mesh_smooth.check_options(**o)),
+    Stage("simplify", mesh_simplify, mesh_simplify.simplify_device, "simplify", 2,
+          lambda o: dict(simplify_voxels=o["voxels"]), _simplify_options,
+          lambda vol, o, views: float(np.float32(o["voxels"] * vol.voxel)),    # the cell; extract aligns it to the volume's origin
+          lambda vol, cell: mesh_simplify.check_options(cell, vol.origin)),
+    Stage("recolour", mesh_colour, mesh_colour.colour_device, "recolour", 4,
+          lambda o: dict(recolour=o), _recolour_options, _recolour_world, _recolour_arguments),
+)
+FLAG_ORDER = tuple(sorted(STAGES, key=lambda stage: stage.since))
+
+
+def stage_keywords(options):
+    """{stage name: check_arguments' options or None} -> the keywords of mesh_depth_maps and mesh_dense_folder that ask for it."""
+    out = {}
+    for stage in STAGES:
+        if options.get(stage.name) is not None:
+            out.update(stage.keywords(options[stage.name]))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ device side
 
 class TsdfVolume:
@@ -287,32 +383,21 @@ class TsdfVolume:
         return self
 
     def extract(self, min_count=1, clean=None, simplify=None, smooth=None, recolour=None):
-        """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation.  With
-        clean = dict(min_faces=, min_extent=, keep_largest=) the mesh goes through mesh_clean.clean_mesh on the device before
-        the copy to the host and the result is (vertices, colours, faces, report).  With simplify = cell (world units) it then
-        goes through mesh_simplify.simplify_device with cells aligned to the volume's origin; the result is (vertices, colours,
-        faces, report) with the simplification's report under "simplify", beside the cleaning's fields if there are any.  With
-        smooth = dict(iterations=, lam=, mu=, boundary=, max_displacement=) (mesh_smooth.check_options) the mesh goes through
-        mesh_smooth.smooth_device after the cleaning and before the simplification; its report goes under "smooth".  With
-        recolour = dict(cams=, images=, and mesh_colour.check_options' options) the mesh, as the last stage, takes its colours
-        from the images through mesh_colour.colour_device (cams at the images' scale); its report goes under "recolour"."""
+        """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32) as numpy; one synchronisation.  The keywords
+        clean, smooth, simplify and recolour (the names of STAGES; a new stage adds its own here) send the mesh through those stages on the device, in the
+        table's order, before the copy to the host; the result is then (vertices, colours, faces, report), the report merged as
+        the table says.  Every stage's value is checked before any GPU work.
+          clean = dict(min_faces=, min_extent=, keep_largest=): mesh_clean.clean_device.
+          smooth = dict(iterations=, lam=, mu=, boundary=, max_displacement=) (mesh_smooth.check_options): mesh_smooth.smooth_device.
+          simplify = cell (world units): mesh_simplify.simplify_device with cells aligned to the volume's origin.
+          recolour = dict(cams=, images=, and mesh_colour.check_options' options), cams at the images' scale:
+          mesh_colour.colour_device."""
         import torch
         from . import _lib
         min_count = check_min_count(min_count)
-        if clean is not None:
-            from . import mesh_clean
-            clean = mesh_clean.check_options(**clean)                          # before any GPU work
-        if simplify is not None:
-            from . import mesh_simplify
-            simplify = mesh_simplify.check_cell(simplify)
-        if smooth is not None:
-            from . import mesh_smooth
-            smooth = mesh_smooth.check_options(**smooth)
-        if recolour is not None:
-            from . import mesh_colour
-            recolour = dict(recolour)
-            views = mesh_colour._view_list(recolour.pop("cams"), recolour.pop("images"))
-            recolour = mesh_colour.check_options(**recolour)
+        given = dict(clean=clean, simplify=simplify, smooth=smooth, recolour=recolour)
+        checked = {stage.name: stage.arguments(self, given[stage.name]) for stage in FLAG_ORDER         # before any GPU work
+                   if given[stage.name] is not None}
         lib = _lib.load()
         nx, ny, nz = self.dims
         nodes = nx * ny * nz
@@ -341,19 +426,10 @@ class TsdfVolume:
                     _lib.ptr(colours), _lib.ptr(faces) if F else None, _lib.ptr(ws), wsb, _lib.stream_ptr())
                 _lib.check(rc, "mvs_surface_nets_write_f32")
             report = None
-            if clean is not None:
-                vertices, colours, faces, report = mesh_clean.clean_device(vertices, colours, faces, self.dev, *clean)
-            if smooth is not None:
-                vertices, colours, faces, smoothed = mesh_smooth.smooth_device(vertices, colours, faces, self.dev, *smooth)
-                report = dict(report or {}, smooth=smoothed)
-            if simplify is not None:
-                vertices, colours, faces, simplified = mesh_simplify.simplify_device(vertices, colours, faces, self.dev, simplify,
-                                                                                     self.origin)
-                report = dict(report or {}, simplify=simplified)
-            if recolour is not None:
-                vertices, colours, faces, recoloured = mesh_colour.colour_device(vertices, colours, faces, self.dev, views[0], views[1],
-                                                                                 *recolour)
-                report = dict(report or {}, recolour=recoloured)
+            for stage in STAGES:
+                if stage.name in checked:
+                    vertices, colours, faces, r = stage.device(vertices, colours, faces, self.dev, *checked[stage.name])
+                    report = dict(report or {}, **(r if stage.key is None else {stage.key: r}))
             mesh = (vertices.cpu().numpy(), colours.cpu().numpy(), faces.cpu().numpy())
             return mesh if report is None else mesh + (report,)
 
@@ -403,28 +479,14 @@ def mesh_depth_maps(depths, probs, cams, images=None, **options):
 
 def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution=None, bounds=None, trunc_voxels=4,
                      num_consistent=3, prob_threshold=0.8, reproj_threshold=1.0, depth_rel_threshold=0.01, sources=None,
-                     min_count=1, device=None, min_component_faces=0, min_component_extent=0.0, keep_largest=0,
-                     simplify_voxels=None, smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed",
-                     smooth_max_voxels=1.0, recolour=None):
-    """mesh_depth_maps -> (vertices, colours, faces, the report of the cleaning, the smoothing and the simplification or None)."""
-    from . import mesh_clean, mesh_simplify, mesh_smooth
-    simplify_voxels = mesh_simplify.check_voxels(simplify_voxels)
-    smooth_iterations = mesh_smooth.check_iterations(smooth_iterations, least=0)
-    smooth = None
-    if smooth_iterations:
-        smooth_max_voxels = mesh_smooth.check_voxels(smooth_max_voxels)
-        mesh_smooth.check_options(smooth_iterations, smooth_lambda, smooth_mu, smooth_boundary)      # before any GPU work
-    if recolour is None or recolour is False:
-        recolour = None
-    else:
-        from . import mesh_colour
-        recolour = {} if recolour is True else dict(recolour)
-        mesh_colour.check_options(**recolour)                                  # before any GPU work
-        if images is None:
-            raise ValueError("recolour needs the images")
+                     min_count=1, device=None, **stage_options):
+    """mesh_depth_maps -> (vertices, colours, faces, the merged report of the stages that ran or None).  stage_options: the
+    keywords that STAGES' rows take (`options`)."""
+    # before any GPU work; the cleaning's keywords are looked at last here, as they have been since they were the only ones
+    options = [(stage, stage.options(stage_options, images)) for stage in FLAG_ORDER[1:] + FLAG_ORDER[:1]]
+    if stage_options:
+        raise TypeError("mesh_depth_maps() got an unexpected keyword argument %r" % sorted(stage_options)[0])
     from .fusion import FusionPlan
-    clean = mesh_clean.check_options(min_component_faces, min_component_extent, keep_largest)
-    clean = dict(zip(mesh_clean.OPTION_NAMES, clean)) if mesh_clean.wanted(*clean) else None
     if voxel is not None and resolution is not None:
         raise ValueError("give a voxel or a resolution, not both")
     tv = float(trunc_voxels)
@@ -452,17 +514,9 @@ def _mesh_depth_maps(depths, probs, cams, images=None, *, voxel=None, resolution
         origin, voxel, dims = choose_volume(bounds[0], bounds[1], voxel, resolution)
     vol = TsdfVolume(origin, voxel, dims, tv * voxel, colour=images is not None, device=device)
     vol.integrate(depths, probs, cams, images, prob_threshold=prob_threshold)
-    if clean is None and simplify_voxels is None and not smooth_iterations and recolour is None:
-        return vol.extract(min_count) + (None,)
-    if recolour is not None:
-        at = [tuple(int(n) for n in im.shape[:2]) for im in images]
-        scaled = np.stack([mesh_colour.scale_cams(np.asarray(cams, np.float64)[k:k + 1], depths.shape[1:3], at[k])[0] for k in range(len(at))])
-        recolour = dict(recolour, cams=scaled, images=images)
-    cell = None if simplify_voxels is None else float(np.float32(simplify_voxels * vol.voxel))
-    if smooth_iterations:
-        smooth = dict(iterations=smooth_iterations, lam=smooth_lambda, mu=smooth_mu, boundary=smooth_boundary,
-                      max_displacement=float(np.float32(smooth_max_voxels * vol.voxel)))
-    return vol.extract(min_count, clean=clean, simplify=cell, smooth=smooth, recolour=recolour)
+    views = (cams, images, depths.shape[1:3])
+    requested = {stage.name: stage.world(vol, o, views) for stage, o in options if o is not None}
+    return vol.extract(min_count, **requested) + (() if requested else (None,))
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -482,14 +536,8 @@ def build_parser():
     ap.add_argument("--fusion_sources", choices=("all", "listed"), default="all",
                     help="consistency against every other view, or the neighbours of pair.txt / covisibility.json")
     ap.add_argument("--force", action="store_true", help="overwrite an existing output file")
-    from .mesh_clean import add_options
-    add_options(ap)
-    from .mesh_simplify import add_option
-    add_option(ap)
-    from .mesh_smooth import add_options as add_smoothing
-    add_smoothing(ap)
-    from .mesh_colour import add_options as add_recolouring
-    add_recolouring(ap)
+    for stage in FLAG_ORDER:
+        stage.module.add_options(ap)
     ap.add_argument("--eval_gt", default=None, help="ground-truth cloud (PLY): evaluate the mesh's surface samples against it "
                     "(mesh_metrics.json beside the output; needs --eval_spacing)")
     from .mesh_sample import add_options as add_sampling
@@ -513,19 +561,7 @@ def parse_args(argv=None):
             raise ValueError("--resolution must be at least 2, got %r" % (a.resolution,))
         if math.isnan(a.prob_threshold) or not a.num_consistent >= 0:
             raise ValueError("--prob_threshold must be a number and --num_consistent >= 0")
-        from .mesh_clean import check_options
-        try:
-            a.min_component_faces, a.min_component_extent, a.keep_largest = check_options(a.min_component_faces,
-                                                                                          a.min_component_extent, a.keep_largest)
-        except ValueError as e:
-            raise ValueError("--min_component_faces and --keep_largest must be integers >= 0, --min_component_extent finite "
-                             "and >= 0 (%s)" % e)
-        if a.simplify_voxels is not None and not (a.simplify_voxels > 0 and math.isfinite(a.simplify_voxels)):
-            raise ValueError("--simplify_voxels must be positive and finite, got %r" % (a.simplify_voxels,))
-        from .mesh_smooth import check_smooth_arguments
-        a.smooth = check_smooth_arguments(a)                                   # None: --smooth_iterations 0, nothing of it runs
-        from .mesh_colour import check_recolour_arguments
-        a.recolour_options = check_recolour_arguments(a)                       # None: no --recolour, nothing of it runs
+        a.stages = {stage.name: stage.module.check_arguments(a) for stage in FLAG_ORDER}  # None: off, nothing of that stage runs
         if (a.eval_gt is None) != (a.eval_spacing is None):
             raise ValueError("--eval_gt and --eval_spacing go together")
         try:
@@ -548,10 +584,7 @@ def parse_args(argv=None):
 
 
 def prepare_output(a):
-    """An existing output is refused without --force, before any GPU work."""
-    if os.path.exists(a.out) and not a.force:
-        raise SystemExit("mvsnet_amd.mesh: %s exists; pass --force to overwrite it" % a.out)
-    return a.out
+    return refuse_existing("mesh", a.out, a.force)
 
 
 def evaluate_mesh(out, vertices, faces, eval_gt, eval_spacing, eval_max_dist=20.0, eval_thresholds=()):
@@ -592,28 +625,14 @@ def mesh_dense_folder(dense_folder, out, *, fusion_sources="all", eval_gt=None, 
     return report
 
 
-def smooth_options(smooth):
-    """check_smooth_arguments' dict (or None) -> the smooth_* options of mesh_depth_maps and mesh_dense_folder."""
-    if smooth is None:
-        return {}
-    return dict(smooth_iterations=smooth["iterations"], smooth_lambda=smooth["lam"], smooth_mu=smooth["mu"],
-                smooth_boundary=smooth["boundary"], smooth_max_voxels=smooth["max_voxels"])
-
-
 def main(argv=None):
     a = parse_args(argv)
     out = prepare_output(a)
-    from ._lib import gpu_ready
-    why = gpu_ready()
-    if why is not None:
-        raise SystemExit("mvsnet_amd.mesh needs a GPU and the HIP library: %s" % why)
+    need_gpu("mesh")
     try:
         report = mesh_dense_folder(a.dense_folder, out, fusion_sources=a.fusion_sources, voxel=a.voxel, resolution=a.resolution,
                                    bounds=a.bounds, trunc_voxels=a.trunc_voxels, num_consistent=a.num_consistent,
-                                   prob_threshold=a.prob_threshold, min_count=a.min_count,
-                                   min_component_faces=a.min_component_faces, min_component_extent=a.min_component_extent,
-                                   keep_largest=a.keep_largest, simplify_voxels=a.simplify_voxels, **smooth_options(a.smooth),
-                                   **({} if a.recolour_options is None else dict(recolour=a.recolour_options)),
+                                   prob_threshold=a.prob_threshold, min_count=a.min_count, **stage_keywords(a.stages),
                                    **({} if a.eval_gt is None else dict(eval_gt=a.eval_gt, eval_spacing=a.eval_spacing,
                                                                         eval_max_dist=a.eval_max_dist, eval_thresholds=a.eval_thresholds)))
     except (ValueError, OSError) as e:

@@ -31,14 +31,14 @@ Semantics (shared by the kernels, tests/mesh_clean_reference.py and the tests).
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import os
 import sys
 
 import numpy as np
 
-MAX_SIZE = 2 ** 31 - 1
+from .mesh_common import inputs, integer, ply_to_ply, refuse_existing, run
+
+WHAT = "mesh cleaning"
 LARGEST = 16
 OPTION_NAMES = ("min_faces", "min_extent", "keep_largest")
 
@@ -49,13 +49,9 @@ def check_options(min_faces=0, min_extent=0.0, keep_largest=0):
     """-> (min_faces, min_extent, keep_largest) as the selection takes them; ValueError otherwise."""
     out = []
     for name, value in (("min_faces", min_faces), ("keep_largest", keep_largest)):
-        try:
-            ok = not isinstance(value, bool) and int(value) == value and int(value) >= 0
-        except (TypeError, ValueError, OverflowError):
-            ok = False
-        if not ok:
+        out.append(integer(value, 0))
+        if out[-1] is None:
             raise ValueError("%s must be an integer >= 0, got %r" % (name, value))
-        out.append(int(value))
     try:
         e = float(min_extent)
     except (TypeError, ValueError):
@@ -70,44 +66,7 @@ def wanted(min_faces=0, min_extent=0.0, keep_largest=0):
     return bool(min_faces or min_extent or keep_largest)
 
 
-def _shapes(vertices, colours, faces):
-    vs, fs = tuple(vertices.shape), tuple(faces.shape)
-    if len(vs) != 2 or vs[1] != 3 or len(fs) != 2 or fs[1] != 3:
-        raise ValueError("vertices must be (M,3) and faces (F,3), got %s and %s" % (vs, fs))
-    if colours is not None and tuple(colours.shape) != vs:
-        raise ValueError("colours must be %s like the vertices, got %s" % (vs, tuple(colours.shape)))
-    if vs[0] > MAX_SIZE or fs[0] > MAX_SIZE:
-        raise ValueError("a mesh of %d vertices and %d faces is beyond the kernels' int32 indices" % (vs[0], fs[0]))
-    return vs[0], fs[0]
-
-
 # ------------------------------------------------------------------------------------------------ device side
-
-def _tensor(x, name, dtype, np_dtype, dev):
-    import torch
-    if x is None:
-        return None
-    if isinstance(x, torch.Tensor):
-        if x.dtype != dtype:
-            raise ValueError("%s must be %s, got %s" % (name, dtype, x.dtype))
-        return x.to(dev).contiguous()
-    return torch.as_tensor(np.ascontiguousarray(np.asarray(x, np_dtype))).to(dev)
-
-
-def _inputs(vertices, colours, faces, device):
-    """-> (device, vertices, colours or None, faces) as contiguous tensors on the device; ValueError for wrong shapes."""
-    import torch
-    from . import _lib
-    for x in (vertices, faces, colours):
-        if x is not None and not hasattr(x, "shape"):
-            raise ValueError("vertices, colours and faces must be arrays or tensors")
-    _shapes(vertices, colours, faces)                                          # before any GPU work
-    if device is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-        device = vertices.device
-    dev = _lib.device(device, "mesh cleaning")
-    return (dev, _tensor(vertices, "vertices", torch.float32, np.float32, dev), _tensor(colours, "colours", torch.uint8, np.uint8, dev),
-            _tensor(faces, "faces", torch.int32, np.int32, dev))
-
 
 class _Components:
     """Labels and measures of one mesh on the device: the two library calls and the table of the components with faces.
@@ -177,7 +136,7 @@ def mesh_components(vertices, faces, device=None):
     """-> dict(face_labels (F,) int32, labels (K,) int32 ascending, faces (K,) int32, lo (K,3), hi (K,3) float32, unreferenced,
     invalid, error_word) as numpy and ints, for the K components with faces."""
     import torch
-    dev, v, _, f = _inputs(vertices, None, faces, device)
+    dev, v, _, f = inputs(vertices, None, faces, device, WHAT)
     with torch.cuda.device(dev):
         comp = _Components(v, f, dev)
         labels, n, lo, hi, _ = comp.table()
@@ -240,23 +199,29 @@ def clean_device(vertices, colours, faces, dev, min_faces=0, min_extent=0.0, kee
 def clean_mesh(vertices, colours, faces, *, min_faces=0, min_extent=0.0, keep_largest=0, device=None):
     """-> (vertices (M',3) float32, colours (M',3) uint8 or None, faces (F',3) int32, report): numpy arrays, or tensors on the
     device when the vertices came as a tensor."""
-    import torch
     options = check_options(min_faces, min_extent, keep_largest)               # before any GPU work
-    dev, v, c, f = _inputs(vertices, colours, faces, device)
-    out_v, out_c, out_f, report = clean_device(v, c, f, dev, *options)
-    if isinstance(vertices, torch.Tensor):
-        return out_v, out_c, out_f, report
-    return out_v.cpu().numpy(), None if out_c is None else out_c.cpu().numpy(), out_f.cpu().numpy(), report
+    return run(vertices, colours, faces, device, WHAT, lambda dev, v, c, f: clean_device(v, c, f, dev, *options))
 
 
 # ------------------------------------------------------------------------------------------------ command line
 
 def add_options(ap, prefix=""):
-    """The three selection options, as mesh.py and depthfusion.py also take them (there under a prefix)."""
-    ap.add_argument("--%smin_component_faces" % prefix, type=int, default=0, help="drop mesh components with fewer faces")
-    ap.add_argument("--%smin_component_extent" % prefix, type=float, default=0.0,
-                    help="drop mesh components whose bounding-box diagonal is shorter, in world units")
-    ap.add_argument("--%skeep_largest" % prefix, type=int, default=0, help="keep only this many of the largest components (0: all)")
+    """The three selection options, as mesh.py and depthfusion.py also take them (there under a prefix) -> their actions."""
+    return [ap.add_argument("--%smin_component_faces" % prefix, type=int, default=0, help="drop mesh components with fewer faces"),
+            ap.add_argument("--%smin_component_extent" % prefix, type=float, default=0.0,
+                            help="drop mesh components whose bounding-box diagonal is shorter, in world units"),
+            ap.add_argument("--%skeep_largest" % prefix, type=int, default=0, help="keep only this many of the largest components (0: all)")]
+
+
+def check_arguments(a, prefix=""):
+    """The three options of add_options on a parsed namespace -> dict(min_faces, min_extent, keep_largest), or None when all
+    three are 0 and nothing of the cleaning runs; ValueError naming the flags otherwise."""
+    try:
+        options = check_options(*(getattr(a, prefix + name) for name in ("min_component_faces", "min_component_extent", "keep_largest")))
+    except ValueError as e:
+        raise ValueError("--%smin_component_faces and --%skeep_largest must be integers >= 0, --%smin_component_extent finite "
+                         "and >= 0 (%s)" % ((prefix,) * 3 + (e,)))
+    return dict(zip(OPTION_NAMES, options)) if wanted(*options) else None
 
 
 def build_parser():
@@ -280,30 +245,13 @@ def parse_args(argv=None):
 
 
 def prepare_output(a):
-    """An existing output is refused without --force, before any GPU work."""
-    if os.path.exists(a.out) and not a.force:
-        raise SystemExit("mvsnet_amd.mesh_clean: %s exists; pass --force to overwrite it" % a.out)
-    return a.out
+    return refuse_existing("mesh_clean", a.out, a.force)
 
 
 def main(argv=None):
     a = parse_args(argv)
-    out = prepare_output(a)
-    from ._lib import gpu_ready
-    from .mesh import read_mesh_ply, write_mesh_ply
-    why = gpu_ready()
-    if why is not None:
-        raise SystemExit("mvsnet_amd.mesh_clean needs a GPU and the HIP library: %s" % why)
-    try:
-        vertices, colours, faces = read_mesh_ply(a.mesh)
-        vertices, colours, faces, report = clean_mesh(vertices, colours, faces, min_faces=a.min_component_faces,
-                                                      min_extent=a.min_component_extent, keep_largest=a.keep_largest)
-        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        write_mesh_ply(out, vertices, colours, faces)
-    except (ValueError, OSError) as e:
-        raise SystemExit("mvsnet_amd.mesh_clean: %s" % e)
-    print(json.dumps(dict(report, out=out)))
-    return 0
+    return ply_to_ply("mesh_clean", a, lambda v, c, f: clean_mesh(v, c, f, min_faces=a.min_component_faces,
+                                                                  min_extent=a.min_component_extent, keep_largest=a.keep_largest))
 
 
 if __name__ == "__main__":

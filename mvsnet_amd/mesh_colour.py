@@ -65,7 +65,10 @@ import sys
 
 import numpy as np
 
-MAX_SIZE = 2 ** 31 - 1
+from . import mesh_common
+from .mesh_common import MAX_SIZE, inputs, integer, need_gpu, number, refuse_existing, run
+
+WHAT = "mesh colouring"
 MAX_AXIS = 1 << 20              # csrc/mesh_colour.hip MC_MAX_AXIS
 MAX_POWER = 8                   # MC_MAX_POWER
 OPTION_NAMES = ("min_cos", "angle_power", "occlusion_rel", "min_depth", "view_chunk")
@@ -81,23 +84,11 @@ _NORMALS_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx
 
 # ------------------------------------------------------------------------------------------------ host side, no GPU needed
 
-def _number(name, value):
-    try:
-        if isinstance(value, bool):
-            raise TypeError
-        return float(value)
-    except (TypeError, ValueError):
-        raise ValueError("%s must be a number, got %r" % (name, value))
-
-
 def _integer(name, value, lo, hi):
-    try:
-        ok = not isinstance(value, bool) and int(value) == value and lo <= int(value) <= hi
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
+    n = integer(value, lo, hi)
+    if n is None:
         raise ValueError("%s must be an integer %d .. %s, got %r" % (name, lo, hi if hi < MAX_SIZE else "2^31-1", value))
-    return int(value)
+    return n
 
 
 def occlusion_ratio(rel):
@@ -110,15 +101,15 @@ def check_options(min_cos=0.2, angle_power=2, occlusion_rel=0.01, min_depth=0.0,
     """-> (min_cos, angle_power, occlusion_rel, min_depth, view_chunk) with min_cos and min_depth exactly float32; ValueError
     otherwise."""
     with np.errstate(over="ignore"):
-        c32 = float(np.float32(_number("min_cos", min_cos)))
+        c32 = float(np.float32(number("min_cos", min_cos)))
     if not 0.0 <= c32 <= 1.0:
         raise ValueError("min_cos must lie in [0, 1] as a float32, got %r" % (min_cos,))
     power = _integer("angle_power", angle_power, 0, MAX_POWER)
-    rel = _number("occlusion_rel", occlusion_rel)
+    rel = number("occlusion_rel", occlusion_rel)
     if not (rel >= 0.0 and math.isfinite(occlusion_ratio(rel))):
         raise ValueError("occlusion_rel must be >= 0 with a finite float32(1 + rel), got %r" % (occlusion_rel,))
     with np.errstate(over="ignore"):
-        md = float(np.float32(_number("min_depth", min_depth)))
+        md = float(np.float32(number("min_depth", min_depth)))
     if not (md >= 0.0 and math.isfinite(md)):
         raise ValueError("min_depth must be >= 0 and finite in float32, got %r" % (min_depth,))
     chunk = _integer("view_chunk", view_chunk, 1, MAX_SIZE)
@@ -199,8 +190,7 @@ def read_mesh_ply_normals(path):
 
 
 def _shapes(vertices, colours, faces):
-    from .mesh_clean import _shapes as shapes
-    M, F = shapes(vertices, colours, faces)
+    M, F = mesh_common.shapes(vertices, colours, faces)
     if 3 * F > MAX_SIZE:
         raise ValueError("a mesh of %d faces has more than 2^31 - 1 corners" % F)
     return M, F
@@ -264,12 +254,8 @@ def vertex_normals(vertices, faces, device=None):
     """Area-weighted vertex normals (step 2 of the module docstring) -> (M,3) float32: a numpy array, or a tensor on the device
     when the vertices came as a tensor."""
     import torch
-    from . import _lib
-    from .mesh_clean import _inputs
-    _shapes(vertices, None, faces)
-    if device is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-        device = vertices.device
-    dev, v, _, f = _inputs(vertices, None, faces, _lib.device(device, "mesh colouring"))
+    _shapes(vertices, None, faces)                                             # first, so that what has no shape is an AttributeError
+    dev, v, _, f = inputs(vertices, None, faces, device, WHAT, _shapes)
     normals = normals_device(v, f, dev)[0]
     return normals if isinstance(vertices, torch.Tensor) else normals.cpu().numpy()
 
@@ -347,34 +333,26 @@ def colour_mesh(vertices, colours, faces, cams, images, device=None, **options):
     """-> (vertices (M,3) float32, colours (M,3) uint8, faces (F,3) int32, report): numpy arrays, or tensors on the device when
     the vertices came as a tensor.  cams (V,2,4,4) at the images' scale; images (V,H,W,3) uint8 or a list of (H,W,3), of any
     sizes; options as check_options takes them, and colour_device's state."""
-    import torch
-    from . import _lib
-    from .mesh_clean import _inputs
     check_options(**{k: v for k, v in options.items() if k != "state"})        # before any GPU work
-    _shapes(vertices, colours, faces)
+    _shapes(vertices, colours, faces)                                          # the mesh before the views; no shape: AttributeError
     _view_list(cams, images)
-    if device is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-        device = vertices.device
-    dev, v, c, f = _inputs(vertices, colours, faces, _lib.device(device, "mesh colouring"))
-    out_v, out_c, out_f, report = colour_device(v, c, f, dev, cams, images, **options)
-    if isinstance(vertices, torch.Tensor):
-        return out_v, out_c, out_f, report
-    return out_v.cpu().numpy(), out_c.cpu().numpy(), out_f.cpu().numpy(), report
+    return run(vertices, colours, faces, device, WHAT, lambda dev, v, c, f: colour_device(v, c, f, dev, cams, images, **options), _shapes)
 
 
 # ------------------------------------------------------------------------------------------------ command line
 
 def add_options(ap, prefix=""):
-    """--recolour and its three numeric companions, as mesh.py and depthfusion.py take them (there under a prefix)."""
-    ap.add_argument("--%srecolour" % prefix, action="store_true",
-                    help="take the mesh's vertex colours from the full-resolution images, as the last stage (mvsnet_amd.mesh_colour)")
-    ap.add_argument("--%srecolour_min_cos" % prefix, type=float, default=0.2, help="recolouring: a view counts from this cosine to the normal on")
-    ap.add_argument("--%srecolour_angle_power" % prefix, type=int, default=2, help="recolouring: a view weighs by the cosine to this power, 0 .. 8")
-    ap.add_argument("--%srecolour_occlusion_rel" % prefix, type=float, default=0.01,
-                    help="recolouring: a vertex this much (relative) behind the rasterised surface is hidden")
+    """--recolour and its three numeric companions, as mesh.py and depthfusion.py take them (there under a prefix) -> their
+    actions."""
+    return [ap.add_argument("--%srecolour" % prefix, action="store_true",
+                            help="take the mesh's vertex colours from the full-resolution images, as the last stage (mvsnet_amd.mesh_colour)"),
+            ap.add_argument("--%srecolour_min_cos" % prefix, type=float, default=0.2, help="recolouring: a view counts from this cosine to the normal on"),
+            ap.add_argument("--%srecolour_angle_power" % prefix, type=int, default=2, help="recolouring: a view weighs by the cosine to this power, 0 .. 8"),
+            ap.add_argument("--%srecolour_occlusion_rel" % prefix, type=float, default=0.01,
+                            help="recolouring: a vertex this much (relative) behind the rasterised surface is hidden")]
 
 
-def check_recolour_arguments(a, prefix=""):
+def check_arguments(a, prefix=""):
     """The options of add_options on a parsed namespace -> dict(min_cos, angle_power, occlusion_rel), or None without
     --recolour (the three are then checked all the same); ValueError naming the flags otherwise."""
     get = lambda name: getattr(a, "%srecolour%s" % (prefix, name))
@@ -417,10 +395,7 @@ def parse_args(argv=None):
 
 
 def prepare_output(a):
-    """An existing output is refused without --force, before any GPU work."""
-    if os.path.exists(a.out) and not a.force:
-        raise SystemExit("mvsnet_amd.mesh_colour: %s exists; pass --force to overwrite it" % a.out)
-    return a.out
+    return refuse_existing("mesh_colour", a.out, a.force)
 
 
 def load_views(a):
@@ -441,10 +416,7 @@ def load_views(a):
 def main(argv=None):
     a = parse_args(argv)
     out = prepare_output(a)
-    from ._lib import gpu_ready
-    why = gpu_ready()
-    if why is not None:
-        raise SystemExit("mvsnet_amd.mesh_colour needs a GPU and the HIP library: %s" % why)
+    need_gpu("mesh_colour")
     import torch
     from . import _lib
     from .mesh import write_mesh_ply
@@ -452,7 +424,7 @@ def main(argv=None):
     try:
         cams, images = load_views(a)
         vertices, colours, faces = read_ply_mesh(a.mesh)
-        dev = _lib.device(None, "mesh colouring")
+        dev = _lib.device(None, WHAT)
         with torch.cuda.device(dev):
             own = t = torch.as_tensor(np.ascontiguousarray(vertices, np.float32)).to(dev)
             if a.mesh_scale != 1.0:

@@ -49,6 +49,9 @@ import sys
 
 import numpy as np
 
+from .mesh_common import inputs, need_gpu, number, refuse_existing, shapes
+
+WHAT = "mesh sampling"
 MAX_VERTICES = 2 ** 31 - 1
 MAX_FACES = 2 ** 26
 MAX_SAMPLES = 2 ** 31 - 1
@@ -60,12 +63,7 @@ STATS_FIELDS = ("faces", "invalid", "zero_area", "samples", "area")
 
 def check_density(density):
     """-> the density as a float; ValueError unless it is a number, finite and > 0."""
-    try:
-        if isinstance(density, bool):
-            raise TypeError
-        d = float(density)
-    except (TypeError, ValueError):
-        raise ValueError("density must be a number, got %r" % (density,))
+    d = number("density", density)
     if not (d > 0 and math.isfinite(d)):
         raise ValueError("density must be positive and finite, got %r" % (density,))
     return d
@@ -74,12 +72,7 @@ def check_density(density):
 def check_spacing(spacing):
     """The spacing s of the command lines -> the density 1.0 / (float(s) * float(s)); ValueError unless s and the density are
     finite and > 0."""
-    try:
-        if isinstance(spacing, bool):
-            raise TypeError
-        s = float(spacing)
-    except (TypeError, ValueError):
-        raise ValueError("spacing must be a number, got %r" % (spacing,))
+    s = number("spacing", spacing)
     d = 1.0 / (s * s) if s > 0 and s * s > 0 else 0.0
     if not (math.isfinite(s) and d > 0 and math.isfinite(d)):
         raise ValueError("spacing must be positive and finite, and so must 1 / spacing^2, got %r" % (spacing,))
@@ -100,7 +93,6 @@ def check_max_samples(max_samples):
 
 
 def _shapes(vertices, colours, faces):
-    from .mesh_clean import _shapes as shapes
     M, F = shapes(vertices, colours, faces)
     if F > MAX_FACES:
         raise ValueError("%d faces are more than the 2^26 that the sampling takes" % F)
@@ -273,16 +265,8 @@ def sample_mesh(vertices, colours, faces, density, seed=0, device=None, *, norma
     """-> ({"xyz", "colours", "normals", "face_index"}, stats): numpy arrays, or tensors on the device when the vertices came
     as a tensor; an output that was not asked for (or colours without input colours) is None."""
     import torch
-    from .mesh_clean import _inputs
     density, seed, max_samples = check_density(density), check_seed(seed), check_max_samples(max_samples)   # before any GPU work
-    for x in (vertices, faces, colours):
-        if x is not None and not hasattr(x, "shape"):
-            raise ValueError("vertices, colours and faces must be arrays or tensors")
-    _shapes(vertices, colours, faces)
-    if device is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-        device = vertices.device
-    from . import _lib
-    dev, v, c, f = _inputs(vertices, colours, faces, _lib.device(device, "mesh sampling"))
+    dev, v, c, f = inputs(vertices, colours, faces, device, WHAT, _shapes)
     out, stats = sample_device(v, c, f, dev, density, seed, normals=normals, face_index=face_index, max_samples=max_samples)
     if not isinstance(vertices, torch.Tensor):
         out = {k: None if t is None else t.cpu().numpy() for k, t in out.items()}
@@ -322,20 +306,14 @@ def parse_args(argv=None):
 
 
 def prepare_output(a):
-    """An existing output is refused without --force, before any GPU work."""
-    if os.path.exists(a.out) and not a.force:
-        raise SystemExit("mvsnet_amd.mesh_sample: %s exists; pass --force to overwrite it" % a.out)
-    return a.out
+    return refuse_existing("mesh_sample", a.out, a.force)
 
 
 def main(argv=None):
     a = parse_args(argv)
     out = prepare_output(a)
-    from ._lib import gpu_ready
+    need_gpu("mesh_sample")
     from .fusion import write_ply
-    why = gpu_ready()
-    if why is not None:
-        raise SystemExit("mvsnet_amd.mesh_sample needs a GPU and the HIP library: %s" % why)
     try:
         vertices, colours, faces = read_ply_mesh(a.mesh)
         cloud, stats = sample_mesh(vertices, colours, faces, a.density, a.seed, normals=a.normals, max_samples=a.max_samples)

@@ -48,14 +48,14 @@ significant first.  Both give the same bytes.
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import os
 import sys
 
 import numpy as np
 
-MAX_SIZE = 2 ** 31 - 1
+from .mesh_common import MAX_SIZE, arrays, number, ply_to_ply, refuse_existing, run, shapes
+
+WHAT = "mesh simplification"
 CELLS = 2 ** 21            # cells per axis; also the number of vertices up to which one int64 holds a face's three clusters
 REPORT_FIELDS = ("vertices_in", "vertices_out", "faces_in", "faces_out", "clusters", "invalid_faces", "degenerate_faces",
                  "duplicate_faces", "unclusterable_vertices", "cell", "origin")
@@ -65,13 +65,7 @@ REPORT_FIELDS = ("vertices_in", "vertices_out", "faces_in", "faces_out", "cluste
 
 def check_cell(cell):
     """-> the cell as a float that is exactly a float32; ValueError unless it is finite and > 0."""
-    try:
-        if isinstance(cell, bool):
-            raise TypeError
-        with np.errstate(over="ignore"):
-            c = float(np.float32(cell))
-    except (TypeError, ValueError):
-        raise ValueError("cell must be a number, got %r" % (cell,))
+    c = number("cell", cell, float32=True)
     if not (c > 0 and math.isfinite(c)):
         raise ValueError("cell must be positive and finite in float32, got %r" % (cell,))
     return c
@@ -90,16 +84,16 @@ def check_origin(origin):
     return o32
 
 
+def check_options(cell, origin):
+    """-> (cell, origin) as simplify_device takes them: check_cell and check_origin."""
+    return check_cell(cell), check_origin(origin)
+
+
 def check_voxels(simplify_voxels):
     """The cell in voxels as the command lines take it: None or 0 is off -> None; else a finite float > 0."""
     if simplify_voxels is None:
         return None
-    try:
-        if isinstance(simplify_voxels, bool):
-            raise TypeError
-        s = float(simplify_voxels)
-    except (TypeError, ValueError):
-        raise ValueError("simplify_voxels must be a number, got %r" % (simplify_voxels,))
+    s = number("simplify_voxels", simplify_voxels)
     if s == 0:
         return None
     if not (s > 0 and math.isfinite(s)):
@@ -125,11 +119,6 @@ def check_extent(lo, hi, cell):
         raise ValueError("the mesh spans %s cells of %g: more than 2^21 on an axis" % ((hi - lo) / float(cell), cell))
 
 
-def _shapes(vertices, colours, faces):
-    from .mesh_clean import _shapes as shapes
-    return shapes(vertices, colours, faces)
-
-
 # ------------------------------------------------------------------------------------------------ device side
 
 def _default_origin(v, F, cell):
@@ -151,8 +140,8 @@ def simplify_device(vertices, colours, faces, dev, cell, origin, two_keys=None):
     device.  two_keys: None chooses by M, True forces the two-key sort of the faces (for tests: both give the same bytes)."""
     import torch
     from . import _lib
-    cell, origin = check_cell(cell), check_origin(origin)
-    M, F = _shapes(vertices, colours, faces)
+    cell, origin = check_options(cell, origin)
+    M, F = shapes(vertices, colours, faces)
     two = M > CELLS if two_keys is None else bool(two_keys)
     if not two and M > CELLS:
         raise ValueError("one key holds the clusters of a face only up to 2^21 vertices, got %d" % M)
@@ -213,14 +202,10 @@ def simplify_mesh(vertices, colours, faces, cell, origin=None, device=None, *, t
     """-> (vertices (M',3) float32, colours (M',3) uint8 or None, faces (F',3) int32, report): numpy arrays, or tensors on the
     device when the vertices came as a tensor."""
     import torch
-    from .mesh_clean import _inputs
     cell = check_cell(cell)                                                    # before any GPU work
     origin = None if origin is None else check_origin(origin)
-    for x in (vertices, faces, colours):
-        if x is not None and not hasattr(x, "shape"):
-            raise ValueError("vertices, colours and faces must be arrays or tensors")
-    M, F = _shapes(vertices, colours, faces)
-    if origin is None and not isinstance(vertices, torch.Tensor):
+    M, F = arrays(vertices, colours, faces)
+    if origin is None and not isinstance(vertices, torch.Tensor):              # arrays place their default origin on the host
         v = np.asarray(vertices, np.float32)
         finite = v[np.isfinite(v).all(1)]
         if len(finite) == 0 and F > 0:
@@ -228,25 +213,35 @@ def simplify_mesh(vertices, colours, faces, cell, origin=None, device=None, *, t
         origin = finite.min(0) if len(finite) else np.zeros(3, np.float32)
         if len(finite):
             check_extent(origin, finite.max(0), cell)
-    if device is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-        device = vertices.device
-    from . import _lib
-    dev, v, c, f = _inputs(vertices, colours, faces, _lib.device(device, "mesh simplification"))
-    with torch.cuda.device(dev):
-        if origin is None:
-            origin = _default_origin(v, F, cell)
-        out_v, out_c, out_f, report = simplify_device(v, c, f, dev, cell, origin, two_keys=two_keys)
-    if isinstance(vertices, torch.Tensor):
-        return out_v, out_c, out_f, report
-    return out_v.cpu().numpy(), None if out_c is None else out_c.cpu().numpy(), out_f.cpu().numpy(), report
+
+    def stage(dev, v, c, f):
+        with torch.cuda.device(dev):
+            return simplify_device(v, c, f, dev, cell, _default_origin(v, F, cell) if origin is None else origin, two_keys=two_keys)
+
+    return run(vertices, colours, faces, device, WHAT, stage)
 
 
 # ------------------------------------------------------------------------------------------------ command line
 
-def add_option(ap, prefix=""):
-    """--simplify_voxels, as mesh.py and depthfusion.py take it (there under a prefix)."""
-    ap.add_argument("--%ssimplify_voxels" % prefix, type=float, default=None,
-                    help="simplify the mesh by vertex clustering in cells of this many voxels (not necessarily an integer)")
+def add_options(ap, prefix=""):
+    """--simplify_voxels, as mesh.py and depthfusion.py take it (there under a prefix) -> its action."""
+    return [ap.add_argument("--%ssimplify_voxels" % prefix, type=float, default=None,
+                            help="simplify the mesh by vertex clustering in cells of this many voxels (not necessarily an integer)")]
+
+
+def check_arguments(a, prefix=""):
+    """The option of add_options on a parsed namespace -> dict(voxels), or None without it; ValueError naming the flag
+    otherwise.  A given 0 is refused here, though check_voxels takes it for "off".  mesh.py and depthfusion.py (the prefix
+    "mesh_") have worded this refusal differently ever since each got the flag, and both wordings are kept."""
+    given = getattr(a, prefix + "simplify_voxels")
+    if given is None:
+        return None
+    try:
+        if check_voxels(given) is None:
+            raise ValueError("0 given")
+    except ValueError as e:
+        raise ValueError("--%ssimplify_voxels must be positive and finite%s" % (prefix, " (%s)" % e if prefix else ", got %r" % (given,)))
+    return dict(voxels=given)
 
 
 def build_parser():
@@ -270,29 +265,12 @@ def parse_args(argv=None):
 
 
 def prepare_output(a):
-    """An existing output is refused without --force, before any GPU work."""
-    if os.path.exists(a.out) and not a.force:
-        raise SystemExit("mvsnet_amd.mesh_simplify: %s exists; pass --force to overwrite it" % a.out)
-    return a.out
+    return refuse_existing("mesh_simplify", a.out, a.force)
 
 
 def main(argv=None):
     a = parse_args(argv)
-    out = prepare_output(a)
-    from ._lib import gpu_ready
-    from .mesh import read_mesh_ply, write_mesh_ply
-    why = gpu_ready()
-    if why is not None:
-        raise SystemExit("mvsnet_amd.mesh_simplify needs a GPU and the HIP library: %s" % why)
-    try:
-        vertices, colours, faces = read_mesh_ply(a.mesh)
-        vertices, colours, faces, report = simplify_mesh(vertices, colours, faces, a.cell, a.origin)
-        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        write_mesh_ply(out, vertices, colours, faces)
-    except (ValueError, OSError) as e:
-        raise SystemExit("mvsnet_amd.mesh_simplify: %s" % e)
-    print(json.dumps(dict(report, out=out)))
-    return 0
+    return ply_to_ply("mesh_simplify", a, lambda v, c, f: simplify_mesh(v, c, f, a.cell, a.origin))
 
 
 if __name__ == "__main__":

@@ -41,14 +41,13 @@ Semantics (shared by the kernels, tests/mesh_smooth_reference.py and the tests).
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import os
 import sys
 
-import numpy as np
+from . import mesh_common
+from .mesh_common import MAX_SIZE, integer, number, ply_to_ply, refuse_existing, run
 
-MAX_SIZE = 2 ** 31 - 1
+WHAT = "mesh smoothing"
 MAX_ITERATIONS = 1000
 BOUNDARIES = ("fixed", "curve", "free")             # the kernels take the index
 OPTION_NAMES = ("iterations", "lam", "mu", "boundary", "max_displacement")
@@ -59,30 +58,17 @@ ROW_FLOATS = 3                                      # the step's row width: (M,3
 
 # ------------------------------------------------------------------------------------------------ host side, no GPU needed
 
-def _float32(name, value):
-    try:
-        if isinstance(value, bool):
-            raise TypeError
-        with np.errstate(over="ignore"):
-            return float(np.float32(value))
-    except (TypeError, ValueError):
-        raise ValueError("%s must be a number, got %r" % (name, value))
-
-
 def check_iterations(iterations, least=1):
-    try:
-        ok = not isinstance(iterations, bool) and int(iterations) == iterations and least <= int(iterations) <= MAX_ITERATIONS
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
+    n = integer(iterations, least, MAX_ITERATIONS)
+    if n is None:
         raise ValueError("iterations must be an integer %d .. %d, got %r" % (least, MAX_ITERATIONS, iterations))
-    return int(iterations)
+    return n
 
 
 def check_options(iterations, lam=0.5, mu=-0.53, boundary="fixed", max_displacement=None):
     """-> (iterations, lam, mu, boundary, max_displacement) with the floats exactly float32; ValueError otherwise."""
     iterations = check_iterations(iterations)
-    l32, m32 = _float32("lam", lam), _float32("mu", mu)
+    l32, m32 = number("lam", lam, float32=True), number("mu", mu, float32=True)
     if not 0 < l32 <= 1:
         raise ValueError("lam must lie in (0, 1] as a float32, got %r" % (lam,))
     if not -1 <= m32 <= 0:
@@ -91,7 +77,7 @@ def check_options(iterations, lam=0.5, mu=-0.53, boundary="fixed", max_displacem
         raise ValueError("boundary must be one of %s, got %r" % (", ".join(BOUNDARIES), boundary))
     r = None
     if max_displacement is not None:
-        r = _float32("max_displacement", max_displacement)
+        r = number("max_displacement", max_displacement, float32=True)
         if not (r > 0 and math.isfinite(r)):
             raise ValueError("max_displacement must be positive and finite in float32, got %r" % (max_displacement,))
     return iterations, l32, m32 + 0.0, boundary, r
@@ -99,20 +85,14 @@ def check_options(iterations, lam=0.5, mu=-0.53, boundary="fixed", max_displacem
 
 def check_voxels(max_voxels):
     """--smooth_max_voxels as the command lines take it: a finite float > 0."""
-    try:
-        if isinstance(max_voxels, bool):
-            raise TypeError
-        s = float(max_voxels)
-    except (TypeError, ValueError):
-        raise ValueError("smooth_max_voxels must be a number, got %r" % (max_voxels,))
+    s = number("smooth_max_voxels", max_voxels)
     if not (s > 0 and math.isfinite(s)):
         raise ValueError("smooth_max_voxels must be positive and finite, got %r" % (max_voxels,))
     return s
 
 
 def _shapes(vertices, colours, faces):
-    from .mesh_clean import _shapes as shapes
-    M, F = shapes(vertices, colours, faces)
+    M, F = mesh_common.shapes(vertices, colours, faces)
     if 6 * F > MAX_SIZE:
         raise ValueError("a mesh of %d faces has more than 2^31 - 1 directed edges" % F)
     return M, F
@@ -168,39 +148,26 @@ def smooth_device(vertices, colours, faces, dev, iterations, lam=0.5, mu=-0.53, 
 def smooth_mesh(vertices, colours, faces, iterations, lam=0.5, mu=-0.53, boundary="fixed", max_displacement=None, device=None):
     """-> (vertices (M,3) float32, colours (M,3) uint8 or None, faces (F,3) int32, report): numpy arrays, or tensors on the
     device when the vertices came as a tensor."""
-    import torch
-    from .mesh_clean import _inputs
     options = check_options(iterations, lam, mu, boundary, max_displacement)   # before any GPU work
-    for x in (vertices, faces, colours):
-        if x is not None and not hasattr(x, "shape"):
-            raise ValueError("vertices, colours and faces must be arrays or tensors")
-    _shapes(vertices, colours, faces)
-    if device is None and isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-        device = vertices.device
-    from . import _lib
-    dev, v, c, f = _inputs(vertices, colours, faces, _lib.device(device, "mesh smoothing"))
-    out_v, out_c, out_f, report = smooth_device(v, c, f, dev, *options)
-    if isinstance(vertices, torch.Tensor):
-        return out_v, out_c, out_f, report
-    return out_v.cpu().numpy(), None if out_c is None else out_c.cpu().numpy(), out_f.cpu().numpy(), report
+    return run(vertices, colours, faces, device, WHAT, lambda dev, v, c, f: smooth_device(v, c, f, dev, *options), _shapes)
 
 
 # ------------------------------------------------------------------------------------------------ command line
 
 def add_options(ap, prefix=""):
-    """--smooth_iterations and its companions, as mesh.py and depthfusion.py take them (there under a prefix)."""
-    ap.add_argument("--%ssmooth_iterations" % prefix, type=int, default=0, help="Taubin smoothing iterations of the mesh (0: none)")
-    ap.add_argument("--%ssmooth_lambda" % prefix, type=float, default=0.5, help="smoothing: the shrinking factor, in (0, 1]")
-    ap.add_argument("--%ssmooth_mu" % prefix, type=float, default=-0.53, help="smoothing: the inflating factor, in [-1, 0] (0: Laplacian)")
-    ap.add_argument("--%ssmooth_boundary" % prefix, choices=BOUNDARIES, default="fixed",
-                    help="smoothing: boundary vertices stay, move along the boundary curve, or move freely")
-    ap.add_argument("--%ssmooth_max_voxels" % prefix, type=float, default=1.0,
-                    help="smoothing: no coordinate moves farther than this many voxels from where the extraction put it")
+    """--smooth_iterations and its companions, as mesh.py and depthfusion.py take them (there under a prefix) -> their actions."""
+    return [ap.add_argument("--%ssmooth_iterations" % prefix, type=int, default=0, help="Taubin smoothing iterations of the mesh (0: none)"),
+            ap.add_argument("--%ssmooth_lambda" % prefix, type=float, default=0.5, help="smoothing: the shrinking factor, in (0, 1]"),
+            ap.add_argument("--%ssmooth_mu" % prefix, type=float, default=-0.53, help="smoothing: the inflating factor, in [-1, 0] (0: Laplacian)"),
+            ap.add_argument("--%ssmooth_boundary" % prefix, choices=BOUNDARIES, default="fixed",
+                            help="smoothing: boundary vertices stay, move along the boundary curve, or move freely"),
+            ap.add_argument("--%ssmooth_max_voxels" % prefix, type=float, default=1.0,
+                            help="smoothing: no coordinate moves farther than this many voxels from where the extraction put it")]
 
 
-def check_smooth_arguments(a, prefix=""):
+def check_arguments(a, prefix=""):
     """The five options of add_options on a parsed namespace -> dict(iterations, lam, mu, boundary, max_voxels), or None when
-    iterations is 0 (the other four are then checked all the same); ValueError naming the flag otherwise."""
+    iterations is 0 (the other four are then checked all the same); ValueError naming the flags otherwise."""
     get = lambda name: getattr(a, "%ssmooth_%s" % (prefix, name))
     try:
         iterations = check_iterations(get("iterations"), least=0)
@@ -238,29 +205,12 @@ def parse_args(argv=None):
 
 
 def prepare_output(a):
-    """An existing output is refused without --force, before any GPU work."""
-    if os.path.exists(a.out) and not a.force:
-        raise SystemExit("mvsnet_amd.mesh_smooth: %s exists; pass --force to overwrite it" % a.out)
-    return a.out
+    return refuse_existing("mesh_smooth", a.out, a.force)
 
 
 def main(argv=None):
     a = parse_args(argv)
-    out = prepare_output(a)
-    from ._lib import gpu_ready
-    from .mesh import read_mesh_ply, write_mesh_ply
-    why = gpu_ready()
-    if why is not None:
-        raise SystemExit("mvsnet_amd.mesh_smooth needs a GPU and the HIP library: %s" % why)
-    try:
-        vertices, colours, faces = read_mesh_ply(a.mesh)
-        vertices, colours, faces, report = smooth_mesh(vertices, colours, faces, a.iterations, a.lam, a.mu, a.boundary, a.max_displacement)
-        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        write_mesh_ply(out, vertices, colours, faces)
-    except (ValueError, OSError) as e:
-        raise SystemExit("mvsnet_amd.mesh_smooth: %s" % e)
-    print(json.dumps(dict(report, out=out)))
-    return 0
+    return ply_to_ply("mesh_smooth", a, lambda v, c, f: smooth_mesh(v, c, f, a.iterations, a.lam, a.mu, a.boundary, a.max_displacement))
 
 
 if __name__ == "__main__":

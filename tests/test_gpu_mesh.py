@@ -224,6 +224,64 @@ def test_scene_to_mesh_end_to_end_equals_the_reference():
     _assert_mesh(vol.extract(), M.scene_mesh("sphere", colour=True))
 
 
+# ------------------------------------------------------------------------------------------------ the whole chain of stages
+
+CHAIN = ("clean", "smooth", "simplify", "recolour")                           # mesh.STAGES' order
+SUBSETS = [tuple(n for k, n in enumerate(CHAIN) if bits >> k & 1) for bits in range(16)]
+
+
+@functools.lru_cache(maxsize=None)
+def _chain_scene():
+    """The noisy sphere, integrated once -> (volume, its plain extraction, extract's value per stage)."""
+    from mvsnet_amd import mesh_colour
+    from tests.test_gpu_mesh_clean import _noisy_volume
+    sc = M.scene("sphere", noisy=True)
+    vol = _noisy_volume("sphere")
+    voxel = float(np.float32(M.SCENE_VOXEL))
+    cams = mesh_colour.scale_cams(sc["cams"], sc["depths"].shape[1:3], sc["images"].shape[1:3])
+    values = dict(clean=dict(min_faces=8), smooth=dict(iterations=3, lam=0.5, mu=-0.53, boundary="fixed", max_displacement=voxel),
+                  simplify=float(np.float32(2 * voxel)), recolour=dict(cams=cams, images=sc["images"]))
+    return vol, vol.extract(), values
+
+
+@functools.lru_cache(maxsize=None)
+def _composed(names):
+    """The public functions of the stages in `names`, one after the other on the plain extraction -> (vertices, colours, faces,
+    {stage: its report}); every chain is computed once and is the start of the longer ones."""
+    from mvsnet_amd import mesh_clean, mesh_colour, mesh_simplify, mesh_smooth
+    vol, plain, values = _chain_scene()
+    if not names:
+        return plain + ({},)
+    v, c, f, reports = _composed(names[:-1])
+    value = values[names[-1]]
+    if names[-1] == "clean":
+        v, c, f, rep = mesh_clean.clean_mesh(v, c, f, **value)
+    elif names[-1] == "smooth":
+        v, c, f, rep = mesh_smooth.smooth_mesh(v, c, f, **value)
+    elif names[-1] == "simplify":
+        v, c, f, rep = mesh_simplify.simplify_mesh(v, c, f, value, vol.origin)
+    else:
+        v, c, f, rep = mesh_colour.colour_mesh(v, c, f, value["cams"], value["images"])
+    return v, c, f, dict(reports, **{names[-1]: rep})
+
+
+@pytest.mark.parametrize("names", SUBSETS, ids=["+".join(s) or "none" for s in SUBSETS])
+def test_extract_with_any_subset_of_the_stages_equals_their_public_functions_in_order(names):
+    vol, plain, values = _chain_scene()
+    got = vol.extract(**{n: values[n] for n in names})
+    v, c, f, reports = _composed(names)
+    assert len(got) == (4 if names else 3)
+    for a, b, what in zip(got, (v, c, f), ("vertices", "colours", "faces")):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (names, what)
+    if names:
+        clean = reports.get("clean", {})
+        assert set(got[3]) == set(clean) | (set(names) - {"clean"})                # clean's fields at top level, the others by name
+        assert {k: got[3][k] for k in clean} == clean
+        for n in names:
+            assert n == "clean" or got[3][n] == reports[n], n
+    assert len(got[0]) > 0 and len(got[2]) > 0 and (got[0].tobytes() != plain[0].tobytes()) == (names not in ((), ("recolour",)))
+
+
 # ------------------------------------------------------------------------------------------------ masks, arguments, commands
 
 @pytest.mark.parametrize("kind", ["plane", "sphere"])

@@ -212,20 +212,20 @@ def test_mesh_and_depthfusion_take_the_prefixed_options():
     import argparse
     from mvsnet_amd import mesh
     a = mesh.parse_args(["--dense_folder", "d"])
-    assert a.recolour_options is None and not a.recolour
+    assert a.stages["recolour"] is None and not a.recolour
     a = mesh.parse_args(["--dense_folder", "d", "--recolour", "--recolour_min_cos", "0.5", "--recolour_angle_power", "4",
                          "--recolour_occlusion_rel", "0.02"])
-    assert a.recolour_options == dict(min_cos=0.5, angle_power=4, occlusion_rel=0.02)
+    assert a.stages["recolour"] == dict(min_cos=0.5, angle_power=4, occlusion_rel=0.02)
     with pytest.raises(SystemExit) as e:
         mesh.parse_args(["--dense_folder", "d", "--recolour_angle_power", "9"])                   # checked without --recolour too
     assert "--recolour_angle_power" in str(e.value) and "0 .. 8" in str(e.value)
     ap = argparse.ArgumentParser()
     MCo.add_options(ap, "mesh_")
     a = ap.parse_args(["--mesh_recolour", "--mesh_recolour_min_cos", "0.3"])
-    assert MCo.check_recolour_arguments(a, "mesh_") == dict(min_cos=float(F32(0.3)), angle_power=2, occlusion_rel=0.01)
-    assert MCo.check_recolour_arguments(ap.parse_args([]), "mesh_") is None
+    assert MCo.check_arguments(a, "mesh_") == dict(min_cos=float(F32(0.3)), angle_power=2, occlusion_rel=0.01)
+    assert MCo.check_arguments(ap.parse_args([]), "mesh_") is None
     with pytest.raises(ValueError, match="--mesh_recolour_min_cos"):
-        MCo.check_recolour_arguments(ap.parse_args(["--mesh_recolour_min_cos", "7"]), "mesh_")
+        MCo.check_arguments(ap.parse_args(["--mesh_recolour_min_cos", "7"]), "mesh_")
 
 
 def test_the_ply_with_normals_round_trips(tmp_path):

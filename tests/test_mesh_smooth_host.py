@@ -206,11 +206,11 @@ def test_the_three_command_lines_check_their_options(tmp_path):
         mesh_smooth.main(["--mesh", src, "--out", out, "--iterations", "1"])
     assert "--force" in str(e.value)
     a = mesh.parse_args(["--dense_folder", str(tmp_path)])                     # --smooth_iterations 0: nothing of it runs
-    assert a.smooth_iterations == 0 and a.smooth is None and mesh.smooth_options(a.smooth) == {}
+    assert a.smooth_iterations == 0 and a.stages["smooth"] is None and mesh.stage_keywords(a.stages) == {}
     a = mesh.parse_args(["--dense_folder", str(tmp_path), "--smooth_iterations", "0", "--smooth_lambda", "0.3"])
-    assert a.smooth is None and mesh.smooth_options(a.smooth) == {}
+    assert a.stages["smooth"] is None and mesh.stage_keywords(a.stages) == {}
     a = mesh.parse_args(["--dense_folder", str(tmp_path), "--smooth_iterations", "10", "--smooth_mu", "-0.4", "--smooth_max_voxels", "2"])
-    assert mesh.smooth_options(a.smooth) == dict(smooth_iterations=10, smooth_lambda=0.5, smooth_mu=float(np.float32(-0.4)),
+    assert mesh.stage_keywords(a.stages) == dict(smooth_iterations=10, smooth_lambda=0.5, smooth_mu=float(np.float32(-0.4)),
                                                  smooth_boundary="fixed", smooth_max_voxels=2.0)
     for bad in (["--smooth_iterations", "-1"], ["--smooth_iterations", "1001"], ["--smooth_iterations", "2", "--smooth_lambda", "2"],
                 ["--smooth_iterations", "2", "--smooth_mu", "nan"], ["--smooth_iterations", "2", "--smooth_max_voxels", "0"],
