@@ -144,6 +144,12 @@ def conv2d_wgrad(x, g, g_off, cout):
     return g_w.permute(2, 3, 1, 0)
 
 
+def flip_t(w):
+    """The kernel of the input gradient of a 3x3 SAME convolution with kernel w (3,3,Cin,Cout): taps flipped, channels
+    transposed -- wgh_t / woh_t of mvs_gru_train_cell_bwd_f32."""
+    return w.flip(0, 1).permute(0, 1, 3, 2).contiguous()
+
+
 def _weight_grads(x, h_prev, rh, gpx, part, Fn):
     """The ten parameter gradients of a cell (CELL_FIELDS order) from the kept px-gradients: batched over all planes."""
     g_wx = conv2d_wgrad(x, gpx, 0, 3 * Fn)
@@ -167,7 +173,6 @@ def _cell_backward(saved, gh, need_x_grad=True):
     Fn = c.shape[-1]
     dev = x.device
     gh = gh.contiguous()
-    flip_t = lambda w: w.flip(0, 1).permute(0, 1, 3, 2).contiguous()      # the kernel of the input gradient
     wgh_t, woh_t = flip_t(wgh), flip_t(woh)
     gpx = torch.empty((D, H, W, 3 * Fn), device=dev, dtype=torch.float32)
     part = torch.zeros((D, 3, slots, 2, Fn), device=dev, dtype=torch.float64)
@@ -282,7 +287,6 @@ class RecurrentCells(torch.autograd.Function):
         main = torch.cuda.current_stream(dev)
         streams = _cell_streams(dev)
         new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
-        flip_t = lambda w: w.flip(0, 1).permute(0, 1, 3, 2).contiguous()      # the kernel of the input gradient
         cb = torch.ops.aten.convolution_backward
         nchw = lambda t: t.permute(0, 3, 1, 2)
         args = ([1, 1], [1, 1], [1, 1], False, [0, 0], 1)

@@ -971,6 +971,8 @@ def test_train_cli_gru_branch(tmp_path, capsys):
 def test_hip_conv_gru_sweep_matches_the_float64_cell_chain(Cin, Fn, dims):
     """mvs_gru_train_cell_fwd_f32 / _bwd_f32 (+ the host's batched convolutions): states and every gradient of one
     ConvGRU cell over all planes against the plane-by-plane concatenated cell of the checker, ragged tile sizes."""
+    # (Whole tensors through the autograd wrapper.  The kept buffers g, c, rh, stats, gpx, part and dh_out element by element, at
+    # the kernels' tile seams, chunked and inside the guarded arena: tests/test_gpu_gru_train_seams.py.)
     from mvsnet_amd import gru_train as G
     D, H, W = dims
     rs = np.random.RandomState(Cin * 100 + Fn)
