@@ -347,6 +347,17 @@ cost_volume_bwd_kernel(const float* __restrict__ ref, const float* __restrict__ 
 // the function pass 1 used (warp_point) and contributes its bilinear weight times its GW row (128 contiguous bytes).
 // A last kernel adds the chunk rows in a fixed order.  No atomics: bit-reproducible, and 2.9 -> ~0.7 ms at N=3,
 // D=192, 120x160 (the float atomics of the scatter version run at ~80 G/s however they are batched).
+//
+// Note on the window and on extreme minification.  Reference pixel p contributes to source pixel s exactly when its sample
+// point lies in the open square s + (-1, 1)^2, i.e. when p lies in the image of that square under the inverse homography.
+// For an affine map that image is inv(s) + J^-1 (du, dv), |du|, |dv| < 1, so |p.x - inv(s).x| < |J^-1_xu| + |J^-1_xv|
+// (and the same in y); pass 2 takes the two columns of J^-1 as forward differences of the inverse map over one source pixel
+// and adds 0.5 pixel for what a projective map departs from its own differences over that square and for the float32
+// rounding of the adjugate.  That margin is the one assumption the window rests on: it is not proven, it is held against
+// the true set of contributors, camera family by camera family, by tests/test_cost_backward_window_host.py.  The
+// half-widths grow with the minification (a source camera of 1/8 the focal length asks for 9.4 pixels), so nothing
+// but the image clips them: an earlier form cut them at 8 pixels and returned success with part of the gradient
+// missing from 8x minification on.  A lane's cost is the window's area, paid only where the geometry asks for it.
 constexpr int CVG_CH1 = 48, CVG_CH2 = 24;            // planes per chunk of pass 1 / pass 2
 
 template <int NSRC>
@@ -407,11 +418,12 @@ cvb_pass2_kernel(const float* __restrict__ transforms, int D, int H, int W, cons
         inv_map(xsf, ysf, px, py); inv_map(xsf + 1.0f, ysf, pxu, pyu); inv_map(xsf, ysf + 1.0f, pxv, pyv);
         // reference pixels within one source pixel of s: |dp| <= |J^-1| (1,1) plus a margin for the curvature
         float bx = fabsf(pxu - px) + fabsf(pxv - px) + 0.5f, by = fabsf(pyu - py) + fabsf(pyv - py) + 0.5f;
-        if (!(bx < 8.0f)) bx = 8.0f;                     // also catches NaN; see the note on extreme minification
-        if (!(by < 8.0f)) by = 8.0f;
         if (!(fabsf(px) < 1e8f) || !(fabsf(py) < 1e8f)) continue;       // the plane does not see this source pixel
-        const int x_lo = max(0, (int)ceilf(px - bx)), x_hi = min(W - 1, (int)floorf(px + bx));
-        const int y_lo = max(0, (int)ceilf(py - by)), y_hi = min(H - 1, (int)floorf(py + by));
+        // the window is bounded by the image alone (the note on extreme minification above); a half-width that is not below
+        // the image extent -- NaN and infinity included -- scans the whole row / column range and keeps the ints finite
+        int x_lo = 0, x_hi = W - 1, y_lo = 0, y_hi = H - 1;
+        if (bx < (float)W) { x_lo = max(0, (int)ceilf(px - bx)); x_hi = min(W - 1, (int)floorf(px + bx)); }
+        if (by < (float)H) { y_lo = max(0, (int)ceilf(py - by)); y_hi = min(H - 1, (int)floorf(py + by)); }
         const float* gwd = gw + ((size_t)v * D + d) * img;
         for (int yy = y_lo; yy <= y_hi; ++yy)
             for (int xx = x_lo; xx <= x_hi; ++xx) {

@@ -431,7 +431,7 @@ int dispatch(const float* big, const float* small, int D, int H, int W, int CB, 
     if (CB == cb && ct == ctv && stride == s) return run<cb, ctv, s, th>(big, small, D, H, W, CS, ws, ws_bytes, dw, need, st);
     WG_CASE(32, 1, 1, 8) WG_CASE(16, 1, 1, 8) WG_CASE(32, 2, 1, 8) WG_CASE(64, 4, 1, 4) WG_CASE(8, 1, 1, 8)
     WG_CASE(32, 1, 2, 4) WG_CASE(16, 2, 2, 4) WG_CASE(32, 4, 2, 4) WG_CASE(8, 1, 2, 4)
-    WG_CASE(16, 1, 2, 4) WG_CASE(64, 2, 2, 4) WG_CASE(8, 1, 1, 8)
+    WG_CASE(16, 1, 2, 4) WG_CASE(64, 2, 2, 4)
 #undef WG_CASE
     return MVS_E_SHAPE;
 }
