@@ -160,6 +160,16 @@ int mvs_homography_transforms_f32(const float* cams, int view_num, int depth_num
  *              (the reference's dead homography_warping path, homography_warping.py:146-149)
  *   cost       (d_count,H,W,C)
  * C must be a multiple of 4.
+ * A sample point that leaves the image, however far (beyond int32 included), contributes 0 for that view and leaves the
+ * other views alone.  Where proj = t6 x + t7 y + 1 is exactly 0 at a pixel, both device routes -- the depth sweep and the
+ * per-plane kernel, chosen by view count, channel count and image size -- and mvs_warp_f32 behave alike:
+ *   numerator != 0   the coordinate is +-inf: outside the image, the view contributes 0 and the voxel stays finite
+ *                    (tf.contrib.image.transform blends the zero taps with inf - inf weights and gives NaN here; the
+ *                    depth sweep's out-of-range weights are literal zeros, and making them carry the NaN cost 1 % of a
+ *                    depth map at the metric workload, so the sweep's behaviour is the contract and the per-plane kernel
+ *                    and the oracle follow it)
+ *   numerator == 0   the coordinate is 0 / 0 = NaN and the voxel is NaN on both routes
+ * (tests/test_gpu_forward_cameras.py, the exact_zero transforms of tests/forward_warp_reference.py).
  */
 int mvs_cost_volume_f32(const float* ref, const float* src, const float* transforms,
                         int view_num, int depth_total, int d_begin, int d_count,

@@ -186,6 +186,11 @@ cost_volume_sweep_kernel(const float* __restrict__ ref, const float* __restrict_
                 const int cb = min(max(ix0, 0), W - 2), rb = min(max(iy0, 0), H - 2);
                 const int dx = ix0 - cb, dy = iy0 - rb;                          // (no overflow: cb, rb >= 0, saturated ix0 / iy0 included)
                 const float fx1 = (x0 + 1.0f) - sx, fx0 = sx - x0, fy1 = (y0 + 1.0f) - sy, fy0 = sy - y0;
+                // proj == 0 (include/mvsnet_hip.h): a +-inf sample point saturates ix0 / iy0, both taps of that axis are outside and carry the
+                // literal 0 below -- the view contributes 0 as for any sample outside the image; a NaN one (0 / 0) converts to 0, takes the
+                // dx == 0 / dy == 0 weights, which are NaN, and the voxel is NaN.  warp_sample<0> gives the same.  (0.0f * fx1 in place of the
+                // literal would make the +-inf case NaN as tf.contrib.image.transform does; two more multiplies here measured 1 % of the
+                // depth map at the metric workload: 1119.5 -> 1108.2 depth maps/s, three runs each.)
                 const float ax = dx == 0 ? fx1 : (dx == -1 ? fx0 : 0.0f), bx = dx == 0 ? fx0 : (dx == 1 ? fx1 : 0.0f);
                 const float ay = dy == 0 ? fy1 : (dy == -1 ? fy0 : 0.0f), by = dy == 0 ? fy0 : (dy == 1 ? fy1 : 0.0f);
                 // 24-bit multiplies (full rate; v_mul_lo_u32 is quarter rate): clamped indices and the strides are < 2^24 (host-checked)
@@ -239,7 +244,8 @@ cost_volume_sweep_kernel(const float* __restrict__ ref, const float* __restrict_
 #pragma unroll
             for (int k = 0; k < Q; ++k) {
                 f32x2 o0, o1;
-                // the negated forms are the same fused multiply-adds with the signs of the operands exchanged: same bits, sign flipped
+                // the negated forms are the same expressions with the signs of the operands exchanged (the compiler picks which product it
+                // fuses per instantiation, so the last bit can differ from the plain form's: tests/test_gpu_forward_cameras.py)
                 if (variant == 0) {
                     const f32x2 s0 = (S[2 * k] * S[2 * k]) * inv_nn, s1 = (S[2 * k + 1] * S[2 * k + 1]) * inv_nn;
                     if (negate) { o0 = s0 - Qs[2 * k] * inv_n; o1 = s1 - Qs[2 * k + 1] * inv_n; }

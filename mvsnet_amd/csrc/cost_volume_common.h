@@ -55,6 +55,10 @@ __device__ __forceinline__ float4 warp_sample(const float* __restrict__ img, con
         float4 v10 = (okx0 && oky1) ? ld4(img + ((size_t)iy1 * W + ix0) * C + c) : z;
         float4 v11 = (okx1 && oky1) ? ld4(img + ((size_t)iy1 * W + ix1) * C + c) : z;
         float wx1 = x1 - sx, wx0 = sx - x0, wy1 = y1 - sy, wy0 = sy - y0;
+        // proj == 0 (include/mvsnet_hip.h): a +-inf coordinate is outside the image like any other -- weights 0, not inf - inf -- as in
+        // the depth sweep, whose out-of-range weights are literal zeros; a NaN coordinate (0 / 0) keeps its NaN weights
+        if (fabsf(sx) == INFINITY) wx1 = wx0 = 0.0f;
+        if (fabsf(sy) == INFINITY) wy1 = wy0 = 0.0f;
         float4 vf, vc, o;
         vf.x = wx1 * v00.x + wx0 * v01.x; vf.y = wx1 * v00.y + wx0 * v01.y;
         vf.z = wx1 * v00.z + wx0 * v01.z; vf.w = wx1 * v00.w + wx0 * v01.w;

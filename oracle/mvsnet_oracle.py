@@ -135,7 +135,8 @@ def image_projective_transform_bilinear(image, t8, dtype=np.float32):
         x0 = floor(sx), x1 = x0+1, y0 = floor(sy), y1 = y0+1
         out = (y1-sy)*[(x1-sx)*I(y0,x0) + (sx-x0)*I(y0,x1)]
             + (sy-y0)*[(x1-sx)*I(y1,x0) + (sx-x0)*I(y1,x1)]
-    where each tap I(.,.) individually reads 0 when its index is outside the image.
+    where each tap I(.,.) individually reads 0 when its index is outside the image, and the weights of an infinite
+    coordinate (p == 0) are 0.
     image: (H, W, C); t8: (8,).
     """
     img = np.asarray(image, dtype=dtype)
@@ -159,10 +160,14 @@ def image_projective_transform_bilinear(image, t8, dtype=np.float32):
         v = img[yi, xi, :]
         return np.where(ok[..., None], v, dtype(0))
 
-    wx1 = (x1f - sx)[..., None]
-    wx0 = (sx - x0f)[..., None]
-    wy1 = (y1f - sy)[..., None]
-    wy0 = (sy - y0f)[..., None]
+    # proj == 0 with a non-zero numerator: the coordinate is +-inf.  TensorFlow's kernel forms inf - inf weights and returns NaN; the
+    # HIP library's contract (include/mvsnet_hip.h, mvs_cost_volume_f32) is that an infinite coordinate is outside the image like
+    # any other and contributes 0, and this restatement follows the library.  0 / 0 stays NaN in both.
+    with np.errstate(invalid="ignore"):
+        wx1 = np.where(np.isinf(sx), dtype(0), x1f - sx)[..., None]
+        wx0 = np.where(np.isinf(sx), dtype(0), sx - x0f)[..., None]
+        wy1 = np.where(np.isinf(sy), dtype(0), y1f - sy)[..., None]
+        wy0 = np.where(np.isinf(sy), dtype(0), sy - y0f)[..., None]
     with np.errstate(invalid="ignore"):
         v_floor = wx1 * read(y0f, x0f) + wx0 * read(y0f, x1f)
         v_ceil = wx1 * read(y1f, x0f) + wx0 * read(y1f, x1f)

@@ -93,11 +93,22 @@ WIDTH_SHAPES = [(27, 41, 16), (19, 35, 19)]          # 'lite' and 'fat', views 0
 VIEW_RANGES = (480.0, 420.0, 360.0)                  # several views per sweep: view v has feature seed v and this depth range
 
 
-def case(width, H, W, D, view=0):
-    """-> dict(features, cams, D, start, end, gp, C): view v of a case has feature seed v and depth range VIEW_RANGES[v]."""
+def case(width, H, W, D, view=0, cams=None):
+    """-> dict(features, cams, D, start, end, gp, C): view v of a case has feature seed v and depth range VIEW_RANGES[v].
+    `cams`: other cameras than the 'small' workload's (3 views at 32 x 48, as family_cams gives them)."""
     C, gp = width_params(width)
-    return dict(features=features(H, W, C, seed=view), cams=small_cams(), D=D, start=DEPTH_START,
+    return dict(features=features(H, W, C, seed=view), cams=small_cams() if cams is None else cams, D=D, start=DEPTH_START,
                 end=depth_end(D, VIEW_RANGES[view]), gp=gp, C=C, key=(width, H, W, D, view))
+
+
+CAMERA_FAMILIES = ("roll90", "random3")              # tests/camera_families.py: the sweep under a turned image and a random pose
+CAMERA_SHAPE = (27, 41, 16)
+
+
+def family_cams(name):
+    """The family's cameras at the 'small' workload's 3 views and 32 x 48 pixels."""
+    from tests import camera_families as CF
+    return CF.make_family_cams(name, 3, 32, 48, 16)
 
 
 def all_cases():
@@ -228,8 +239,8 @@ def plane_scores(features, cams, D, start, end, gp, inverse=False):
     return _CACHE[key]
 
 
-def case_scores(width, H, W, D, view=0):
-    c = case(width, H, W, D, view)
+def case_scores(width, H, W, D, view=0, cams=None):
+    c = case(width, H, W, D, view, cams)
     return c, plane_scores(c["features"], c["cams"], c["D"], c["start"], c["end"], c["gp"], False)
 
 

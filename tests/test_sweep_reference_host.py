@@ -61,6 +61,26 @@ def test_float32_reference_stays_inside_the_bound(key):
     R.check_every_pixel(d, p, ref, "float32 +-4 ulp " + ids(key))
 
 
+@pytest.mark.parametrize("name", R.CAMERA_FAMILIES)
+def test_float32_reference_stays_inside_the_bound_under_camera_families(name):
+    """The two camera cases of tests/test_gpu_forward_cameras.py: the same two evaluations under roll90 and random3."""
+    c, ref = R.case_scores("normal", *R.CAMERA_SHAPE, cams=R.family_cams(name))
+    assert not np.array_equal(c["cams"], R.small_cams())
+    R.check_every_pixel(ref.depth32, ref.prob32, ref, "float32 " + name)
+    rs = np.random.RandomState(11)
+    d, p, reg = R.sweep(c["features"], c["cams"], c["D"], c["start"], c["end"], c["gp"], False, np.float32, act=R.perturb_ulps(rs, 4))
+    score = float(np.abs(reg.astype(np.float64) - ref.reg64).max()) / ref.E
+    print("perturbed scores: %.2f E" % score)
+    assert score <= 2.0, score
+    R.check_every_pixel(d, p, ref, "float32 +-4 ulp " + name)
+
+
+def test_default_cameras_of_a_case_are_unchanged():
+    c = R.case("normal", 5, 11, 17)
+    assert np.array_equal(c["cams"], R.small_cams())
+    assert R.case_scores("normal", 5, 11, 17)[1] is R.case_scores("normal", 5, 11, 17, cams=R.small_cams())[1]
+
+
 # ---- planted faults ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def base():
